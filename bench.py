@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput of the phase-3 audio-conditioned WGAN-GP training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one loop body of phase3/train.py:186-243 on one synthetic batch already
@@ -11,7 +11,11 @@ every n_critic_steps-th step (8, phase3/configs/default.yaml) — so K should be
 of 8 to time whole cycles. Workload = BASELINE.json configs[2]: default conv1d encoder,
 120-frame sequences, batch 64 per GPU (weak scaling: the global batch is 64 * N).
 
-Rank 0 prints ONE JSON line: seq/s over all GPUs, plus
+Rank 0 prints ONE JSON line: seq/s over all GPUs and ms per timed step. A plain run does only that: set up, warm
+up, time the K steps, write the last step's outputs (--dump-outputs DIR: DIR/<name>.npy, float32) and print the line.
+--full adds what takes runs or passes of its own:
+  other_configs / clock_GHz_in_step — the c2 / c4 / c5 presets and the stamped library's shader clock (child processes
+                 started before this process touches the GPU; default workload, one GPU);
   roofline     — the implicit-GEMM engine (conv1d fwd/bwd_data/bwd_weight + linear GEMMs):
                  sum of 2*M*N*K over its launches / sum of their HIP-event durations,
                  measured inside the timed region on the launch stream, against the exact
@@ -299,7 +303,7 @@ def other_configs(steps=16, warmup=8):
     out = {}
     for name in ("c2", "c4", "c5"):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", str(warmup),
-               "--no-cpu-baseline", "--no-other-configs"] + (["--parity-check"] if name == "c2" else [])
+               "--full", "--no-cpu-baseline", "--no-other-configs"] + (["--parity-check"] if name == "c2" else [])
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=float(os.environ.get("M2D_OTHER_TIMEOUT", "240")))
@@ -431,6 +435,36 @@ def self_launch(args):
         sys.exit("bench.py: %s" % (failed or "ranks failed (rank, exit code): %s" % bad))
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: every file of DIR together, headers included
+
+
+def dump_outputs(d, engine, gen, critic):
+    """What the timed path computed in its last step, as d/<name>.npy in float32: the step's scalars (`step.<key>`, what
+    train_step returned) and every floating-point parameter and buffer of the generator and the critic after it
+    (`gen.<key>`, `critic.<key>`, state_dict names). If they exceed DUMP_LIMIT_BYTES, each array keeps the same share of
+    its elements, at indices drawn from a generator seeded by the array's name: the same sample in every run."""
+    import zlib
+    import numpy as np
+    arrays = {"step." + k: v for k, v in engine.last.items()}
+    for prefix, m in (("gen", gen), ("critic", critic)):
+        for k, v in m.state_dict().items():
+            if v.is_floating_point():
+                arrays["%s.%s" % (prefix, k)] = v
+    header = 128  # the .npy header of a 1-D or 0-D float32 array
+    total = sum(4 * v.numel() + header for v in arrays.values())
+    share = 1.0 if total <= DUMP_LIMIT_BYTES else (DUMP_LIMIT_BYTES - header * len(arrays)) / (total - header * len(arrays))
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        a = v.detach().float().cpu()
+        if share < 1.0:
+            a = a.reshape(-1)
+            k = int(a.numel() * share)
+            if k < a.numel():
+                g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+                a = a[torch.randperm(a.numel(), generator=g)[:k].sort().values]
+        np.save(os.path.join(d, name + ".npy"), a.numpy().astype(np.float32))
+
+
 PEAK_HBM_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 FAMILIES = ["gemm", "bn", "gru", "pointwise", "reduce"]
 
@@ -504,7 +538,16 @@ def main():
                     help="presets that have one (c2): replay a short oracle trace at the bench size on the GPU afterwards")
     ap.add_argument("--phase", type=int, default=3, choices=[1, 2, 3],
                     help="which train script's loop body (3 = the BASELINE metric; 1 / 2: --config c1 / c2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs or passes of its own: the other presets, the shader "
+                         "clock, the per-launch roofline pass and its probes, the CPU baseline and its parity replay "
+                         "(--no-* above switch single parts off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): its "
+                         "scalars and the generator's / critic's parameters and buffers after it")
     args = ap.parse_args()
+    if args.dump_shapes and not args.full:
+        ap.error("--dump-shapes writes the roofline pass's table: it needs --full")
     if args.config:
         for k, v in PRESETS[args.config].items():
             if k == "graphs" and args.graphs is not None:
@@ -521,7 +564,7 @@ def main():
     # process's idle HIP context alive beside the child, the launch-bound c2 loop ran 13 % slower: 15.2 k vs 17.5 k
     # seq/s) - and none of it overlaps this workload's timed region.
     others = clock = None
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_other_configs and args.phase == 3 and
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_other_configs and args.phase == 3 and
             (args.enc_type, args.frames, args.ablated, args.batch) == ("default", 120, False, 64)):
         others = other_configs()
         clock = step_clock()
@@ -638,6 +681,8 @@ def main():
     # the wait diagnostics of the timed steps, read now (the device is idle; the roofline pass below adds its own)
     waits = {n: getattr(engine, n).wait_stats() for n in ("x_critic", "x_gen") if getattr(engine, n, None) is not None}
     waits["join"] = engine.join_stats() if hasattr(engine, "join_stats") else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine, gen, critic)  # before any pass below moves the weights on
     step_ms = [a.elapsed_time(b) for a, b in zip(step_events, step_events[1:])]
     if os.environ.get("M2D_STEP_TIMES"):  # dev aid: per-step GPU time to stderr
         print("step ms:", " ".join("%.2f" % v for v in step_ms), file=sys.stderr)
@@ -656,7 +701,7 @@ def main():
     # 20.3 vs 18.7 ms per step), so they stay out of the region `value` is timed on; the kernels,
     # their order and their inputs are the same.
     prof = None
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         if args.graphs == "on":
             engine.enable_graphs(False)  # graph replays carry no per-launch events
         # the timed region runs the critic's pose branch on a side stream under the audio branch; an
@@ -876,7 +921,7 @@ def main():
                     "gflop_per_seq_cycle": ref_gf,
                     "step_tflops": round(ref_gf * 1e9 * whole_cycles["value"] / 1e12, 2)}
         default_cfg = args.phase == 3 and (args.enc_type, args.frames, args.ablated) == ("default", 120, False)
-        if not args.no_cpu_baseline and world == 1 and default_cfg:
+        if args.full and not args.no_cpu_baseline and world == 1 and default_cfg:
             pay = None
             try:
                 out["cpu_baseline"] = cpu_baseline()

@@ -24,6 +24,19 @@ def gen(*shape, seed=0, scale=1.0):
     return (torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale).to(DEV)
 
 
+# the audio critic's k25 / stride-4 layers (tap-vectorised forward, sub-pixel backward-data), the encoder's k3 layers,
+# a strided U-Net-like layer, the single-channel first layer (thin kernels)
+CONV_LAYERS = [("k25s4 64->128", (4, 64, 128, 1024, 25, 4, 11)), ("k25s4 16->32", (6, 16, 32, 2048, 25, 4, 11)),
+               ("k3 256->512", (40, 256, 512, 24, 3, 1, 1)), ("k4s2 32->64", (8, 32, 64, 500, 4, 2, 1)),
+               ("k25s4 1->32", (6, 1, 32, 4096, 25, 4, 11)), ("k25 69->128", (6, 69, 128, 120, 25, 1, 12)),
+               ("k250s50 1->32", (24, 1, 32, 3200, 250, 50, 124)), ("k160s4 1->32", (5, 1, 32, 3200, 160, 4, 79))]
+CONV_FORMS = ["fwd", "fwd+stats", "bwd_data", "bwd_weight"]
+OTHER_CASES = ["linear 480x256x256", "linear weight gradient", "head 6x100x38400", "bn_stats rows", "bn_stats long",
+               "channel_sums"]
+# the case names need no device: every machine collects the same test ids (the cases skip where no GPU is visible)
+CASE_NAMES = sorted(["conv %s %s" % (name, form) for name, _ in CONV_LAYERS for form in CONV_FORMS] + OTHER_CASES)
+
+
 def conv_case(B, Cin, Cout, L, ks, stride, pad):
     x, w = gen(B, Cin, L, seed=1), gen(Cout, Cin, ks, seed=2, scale=1.0 / math.sqrt(Cin * ks))
     b = gen(Cout, seed=3, scale=0.1)
@@ -39,12 +52,7 @@ def conv_case(B, Cin, Cout, L, ks, stride, pad):
 
 def cases():
     out = {}
-    # the audio critic's k25 / stride-4 layers (tap-vectorised forward, sub-pixel backward-data), the encoder's k3 layers,
-    # a strided U-Net-like layer, the single-channel first layer (thin kernels)
-    for name, args in [("k25s4 64->128", (4, 64, 128, 1024, 25, 4, 11)), ("k25s4 16->32", (6, 16, 32, 2048, 25, 4, 11)),
-                       ("k3 256->512", (40, 256, 512, 24, 3, 1, 1)), ("k4s2 32->64", (8, 32, 64, 500, 4, 2, 1)),
-                       ("k25s4 1->32", (6, 1, 32, 4096, 25, 4, 11)), ("k25 69->128", (6, 69, 128, 120, 25, 1, 12)),
-                       ("k250s50 1->32", (24, 1, 32, 3200, 250, 50, 124)), ("k160s4 1->32", (5, 1, 32, 3200, 160, 4, 79))]:
+    for name, args in CONV_LAYERS:
         for form, f in conv_case(*args).items():
             out["conv %s %s" % (name, form)] = f
     a, b, bias = gen(480, 256, seed=5), gen(256, 256, seed=6, scale=1 / 16.0), gen(256, seed=7)
@@ -58,6 +66,7 @@ def cases():
     x3 = gen(6, 64, 2000, seed=14)
     out["bn_stats long"] = lambda: K().bn_stats(x3)
     out["channel_sums"] = lambda: K().channel_sums(x3)
+    assert sorted(out) == CASE_NAMES, sorted(set(out) ^ set(CASE_NAMES))
     return out
 
 
@@ -78,7 +87,7 @@ def _flat(o):
     return [t for t in (o if isinstance(o, (tuple, list)) else (o,)) if torch.is_tensor(t)]
 
 
-@pytest.mark.parametrize("name", sorted(cases().keys()) if torch.cuda.is_available() else [])
+@pytest.mark.parametrize("name", CASE_NAMES)
 def test_bit_equal_beside_a_gemm_on_another_stream(name, busy):
     f = cases()[name]
     with K().weight_cache():

@@ -1,4 +1,4 @@
-"""Dev tool: diff two per-shape tables written by `bench.py --dump-shapes` (same box, two settings): ms per step by shape."""
+"""Dev tool: diff two per-shape tables written by `bench.py --full --dump-shapes` (same box, two settings): ms per step by shape."""
 import csv, sys
 def load(p):
     d = {}
