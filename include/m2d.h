@@ -8,6 +8,8 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer to fp32 (int32 for `lengths`) owned by the caller;
+ *     the one exception is the cross-entropy family, whose `labels` and `pred` are int64
+ *     (torch's class-index dtype);
  *     tensors are dense row-major in the reference's own layouts: activations (B, C, L),
  *     conv weights (Cout, Cin, k), linear weights (out, in), sequences (B, T, H);
  *   - `stream` is a hipStream_t passed as void*; calls only enqueue on it: no allocation,
@@ -287,6 +289,33 @@ int m2d_gru_stack_bwd(const float* dout, const float* const* out, const float* c
 /* `counters` of m2d_gru_stack_bwd (optional, m2d_gru_stack_counters(B, L) unsigneds of scratch owned by the call): with
  * them the whole back-propagation through time runs as ONE persistent launch too (round 3): weight slices in LDS,
  * dgh_l[t+1] / dgi_{l+1}[t] handed over between CUs inside the launch; bit-identical to the per-step launches. */
+
+/* ---- small-state GRU (1 <= H <= 16; H outside gives M2D_ERR_ARG) --------------------------
+ * reference: nn.GRU(128, 4) of RecurrentDanceClassifier, dance_classification/archis/default.py:18,24, whose
+ * final state h_n is the logits. One layer, the whole sequence in ONE launch: one batch row per 16-lane group,
+ * W_hh / b_hh in registers, h broadcast inside the group. gi = x W_ih^T + b_ih comes from m2d_gemm (mode 0);
+ * w_hh is (3H, H) as nn.GRU stores it. out (B, T, H) or NULL: rows past lengths[b] are 0, as in
+ * m2d_gru_layer_fwd. h_n (B, H): the state after step lengths[b] - 1 (T - 1 without lengths) - torch's h_n.
+ * saved (4, B, T, H) or NULL: r, z, n, W_hn h + b_hn (the layout of m2d_gru_stack_fwd).
+ * The backward (BPTT, one launch) takes dout (B, T, H) and / or dh_n (B, H) (either may be NULL), the forward's
+ * out (required: it holds h_{t-1}) and saved state, and writes dgi and dgh (B, T, 3H) with the contract of
+ * m2d_gru_layer_bwd: weight, bias and input gradients then come from m2d_gemm modes 1 / 2 and m2d_channel_sums. */
+int m2d_gru_small_fwd(const float* gi, const float* w_hh, const float* b_hh, const int* lengths, float* out,
+                      float* h_n, float* saved, int B, int T, int H, void* stream);
+int m2d_gru_small_bwd(const float* dout, const float* dh_n, const float* out, const float* saved, const float* w_hh,
+                      const int* lengths, float* dgi, float* dgh, int B, int T, int H, void* stream);
+
+/* ---- softmax cross-entropy (torch.nn.CrossEntropyLoss, mean; dance_classification/main.py:126) ----------
+ * logits (B, C), C <= 1024 (M2D_ERR_ARG beyond); labels int64 (B); loss: one float (0-dim). Max-subtracted
+ * log-sum-exp per row, the per-row losses summed in fp64 in a fixed order (bit-stable from run to run).
+ * pred (int64 (B) or NULL): the argmax, first maximum on ties (torch.argmax). A label outside [0, C) makes the
+ * loss (and that row's gradient) NaN; nothing asserts on the device. ws: m2d_cross_entropy_workspace_bytes.
+ * The backward writes dlogits = (softmax - onehot) * gout[0] / B, gout a device scalar. */
+size_t m2d_cross_entropy_workspace_bytes(int B, int C);
+int m2d_cross_entropy_fwd(const float* logits, const long long* labels, float* loss, long long* pred, int B, int C,
+                          void* ws, size_t ws_bytes, void* stream);
+int m2d_cross_entropy_bwd(const float* logits, const long long* labels, const float* gout, float* dlogits, int B,
+                          int C, void* stream);
 
 /* ---- gradient penalty (losses.py:5-60) ----------------------------------------------------- */
 int m2d_gp_interpolate(const float* real, const float* fake, const float* alpha, float* out, int B, int n,

@@ -86,6 +86,11 @@ SIGNATURES = {
     "m2d_gru_persist_raise": (_I, []),
     "m2d_fault_fetch": (_I, [_F, _F]),
     "m2d_gru_stack_bwd": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _F, _F]),
+    "m2d_gru_small_fwd": (_I, [_F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _F]),
+    "m2d_gru_small_bwd": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _F]),
+    "m2d_cross_entropy_workspace_bytes": (_S, [_I, _I]),
+    "m2d_cross_entropy_fwd": (_I, [_F, _F, _F, _F, _I, _I, _F, _S, _F]),
+    "m2d_cross_entropy_bwd": (_I, [_F, _F, _F, _F, _I, _I, _F]),
     "m2d_gp_interpolate": (_I, [_F, _F, _F, _F, _I, _I, _F]),
     "m2d_gp_penalty_workspace_bytes": (_S, [_I]),
     "m2d_gp_penalty_fwd": (_I, [_F, _F, _F, _I, _I, _I, _F, _S, _F]),

@@ -1165,3 +1165,304 @@ int m2d_gru_stack_bwd(const float* dout, const float* const* out, const float* c
 }
 
 }  // extern "C"
+
+// =========================================================================================
+// Small-state GRU (1 <= H <= 16): the dance classifier's nn.GRU(128, 4), whose final state is
+// the logits (dance_classification/archis/default.py:21,27). The step kernels above give a block
+// 16 units x 16 rows and hand h between steps through LDS and a launch boundary; at H = 4 twelve
+// of every sixteen units idle and each step is pure latency. Here one batch row owns one 16-lane
+// group of a wave (4 rows per wave) for the WHOLE sequence, in one launch: lane j keeps unit j's
+// rows of W_hh and b_hh in registers and h_{t-1} is broadcast inside the group by ds_bpermute
+// (__shfl). No LDS, no barrier.
+// Lanes j >= H carry zero weights and h = 0, so every sum runs over all 16 lanes with constant
+// register indices (a runtime trip count would index the weight arrays dynamically: scratch).
+//
+// Memory runs one chunk of GRU_SMALL_CH steps ahead of the math. On gfx9 loads and stores share
+// vmcnt and the compiler waits for vmcnt(0) as soon as both kinds are in flight, so a per-step
+// prefetch next to per-step stores waits a full round trip every step. Instead, at the top of a
+// chunk the wave issues the stores of the PREVIOUS chunk's results and the loads of the NEXT
+// chunk's operands, then runs the chunk's steps on registers only (cross-lane reads wait on
+// lgkmcnt, not vmcnt), then waits once (vmcnt(0)) for traffic that had the whole chunk to land.
+// Every load and store is an unconditional raw buffer access: lanes outside the sequence, the
+// hidden size or the batch get the offset M2D_OOB, which the hardware range check turns into a
+// 0.0f load / a dropped store, and a NULL output gets a zero-sized resource - no divergent branch
+// around memory, so the waits stay where they are written.
+#define GRU_SMALL_MAX 16
+#define GRU_SMALL_CH 8
+#define GRU_OOB 0x80000000u
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t gru_rsrc(const float* p, size_t nbytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, p ? (int)nbytes : 0, 0x00020000);
+}
+__device__ __forceinline__ float gru_bload(__amdgpu_buffer_rsrc_t r, unsigned voff) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, 0));
+}
+__device__ __forceinline__ void gru_bstore(float v, __amdgpu_buffer_rsrc_t r, unsigned voff) {
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, 0, 0);
+}
+// s_waitcnt vmcnt(0) (expcnt / lgkmcnt left alone): the one wait of a chunk
+__device__ __forceinline__ void gru_wait_vm() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
+__global__ void __launch_bounds__(64) m2d_gru_small_fwd_kernel(const float* __restrict__ gi,
+                                                               const float* __restrict__ w_hh,
+                                                               const float* __restrict__ b_hh,
+                                                               const int* __restrict__ lengths, float* out,
+                                                               float* h_n, float* saved, int B, int T, int H) {
+  const int lane = threadIdx.x;
+  const int j = lane & 15;
+  const int grp = lane >> 4;
+  const int base = lane & 48;
+  const int b0 = blockIdx.x * 4;
+  const int b = b0 + grp;
+  const int rows = min(4, B - b0);
+  const bool row = b < B;
+  const bool act = row && j < H;
+  float wr[GRU_SMALL_MAX], wz[GRU_SMALL_MAX], wn[GRU_SMALL_MAX];
+#pragma unroll
+  for (int k = 0; k < GRU_SMALL_MAX; ++k) {
+    const bool ok = act && k < H;
+    wr[k] = ok ? w_hh[(size_t)j * H + k] : 0.f;
+    wz[k] = ok ? w_hh[(size_t)(H + j) * H + k] : 0.f;
+    wn[k] = ok ? w_hh[(size_t)(2 * H + j) * H + k] : 0.f;
+  }
+  const float bhr = act ? b_hh[j] : 0.f, bhz = act ? b_hh[H + j] : 0.f, bhn = act ? b_hh[2 * H + j] : 0.f;
+  int len = T;
+  if (row && lengths) len = min(max(lengths[b], 0), T);
+  // resources cover this wave's rows only; offsets are bytes from the wave's first row
+  const size_t BTH = (size_t)B * T * H, rowT = (size_t)rows * T;
+  const __amdgpu_buffer_rsrc_t rg = gru_rsrc(gi + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
+  const __amdgpu_buffer_rsrc_t ro = gru_rsrc(out ? out + (size_t)b0 * T * H : nullptr, rowT * H * 4);
+  __amdgpu_buffer_rsrc_t rs[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) rs[p] = gru_rsrc(saved ? saved + p * BTH + (size_t)b0 * T * H : nullptr, rowT * H * 4);
+  const unsigned gbase = 4u * ((unsigned)grp * T * 3 * H + j), obase = 4u * ((unsigned)grp * T * H + j);
+  auto goff = [&](int t) { return (act && t >= 0 && t < T) ? gbase + 4u * (unsigned)(t * 3 * H) : GRU_OOB; };
+  auto ooff = [&](int t) { return (act && t >= 0 && t < T) ? obase + 4u * (unsigned)(t * H) : GRU_OOB; };
+
+  float cg[GRU_SMALL_CH][3], ng[GRU_SMALL_CH][3];  // gi of this chunk / of the next one
+  float po[5][GRU_SMALL_CH];                        // h, r, z, n, W_hn h + b_hn of the previous chunk
+#pragma unroll
+  for (int s = 0; s < GRU_SMALL_CH; ++s) {
+    const unsigned o = goff(s);
+    cg[s][0] = gru_bload(rg, o);
+    cg[s][1] = gru_bload(rg, o + 4u * H);
+    cg[s][2] = gru_bload(rg, o + 8u * H);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) po[q][s] = 0.f;
+  }
+  gru_wait_vm();
+  float h = 0.f, hlast = 0.f;
+  for (int c0 = 0; c0 < T; c0 += GRU_SMALL_CH) {
+    // the previous chunk's results leave, the next chunk's operands arrive, while this chunk computes
+#pragma unroll
+    for (int s = 0; s < GRU_SMALL_CH; ++s) {
+      const unsigned o = ooff(c0 - GRU_SMALL_CH + s);
+      gru_bstore(po[0][s], ro, o);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) gru_bstore(po[1 + p][s], rs[p], o);
+    }
+#pragma unroll
+    for (int s = 0; s < GRU_SMALL_CH; ++s) {
+      const unsigned o = goff(c0 + GRU_SMALL_CH + s);
+      ng[s][0] = gru_bload(rg, o);
+      ng[s][1] = gru_bload(rg, o + 4u * H);
+      ng[s][2] = gru_bload(rg, o + 8u * H);
+    }
+#pragma unroll
+    for (int s = 0; s < GRU_SMALL_CH; ++s) {
+      const int t = c0 + s;
+      float hk[GRU_SMALL_MAX];
+#pragma unroll
+      for (int k = 0; k < GRU_SMALL_MAX; ++k) hk[k] = __shfl(h, base + k, 64);
+      float sr = 0.f, sz = 0.f, sn = 0.f;
+#pragma unroll
+      for (int k = 0; k < GRU_SMALL_MAX; ++k) {
+        sr += wr[k] * hk[k];
+        sz += wz[k] * hk[k];
+        sn += wn[k] * hk[k];
+      }
+      const float hn = sn + bhn;
+      const float r = gru_sigmoid(cg[s][0] + (sr + bhr));
+      const float z = gru_sigmoid(cg[s][1] + (sz + bhz));
+      const float n = tanhf(cg[s][2] + r * hn);
+      float hnew = (1.f - z) * n + z * h;
+      if (t >= len) hnew = 0.f;
+      po[0][s] = hnew, po[1][s] = r, po[2][s] = z, po[3][s] = n, po[4][s] = hn;
+      if (t == len - 1) hlast = hnew;
+      if (t < T) h = act ? hnew : 0.f;
+    }
+    gru_wait_vm();
+#pragma unroll
+    for (int s = 0; s < GRU_SMALL_CH; ++s) cg[s][0] = ng[s][0], cg[s][1] = ng[s][1], cg[s][2] = ng[s][2];
+  }
+  const int clast = ((T - 1) / GRU_SMALL_CH) * GRU_SMALL_CH;  // first step of the last chunk
+#pragma unroll
+  for (int s = 0; s < GRU_SMALL_CH; ++s) {
+    const unsigned o = ooff(clast + s);
+    gru_bstore(po[0][s], ro, o);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) gru_bstore(po[1 + p][s], rs[p], o);
+  }
+  if (act) h_n[(size_t)b * H + j] = hlast;
+}
+
+// BPTT of the kernel above, one launch: dL/dh stays in registers across steps. Lane j keeps COLUMN j of
+// W_hh (the three gate blocks), so (W_hh^T dg)_j = sum_i dg_i W_hh[i][j] is a broadcast of the group's
+// 3H pre-activation gradients plus a register dot product. Writes dgi / dgh exactly as m2d_gru_layer_bwd.
+// Same chunked memory schedule as the forward, walking time downwards.
+__global__ void __launch_bounds__(64) m2d_gru_small_bwd_kernel(const float* __restrict__ dout,
+                                                               const float* __restrict__ dh_n,
+                                                               const float* __restrict__ out,
+                                                               const float* __restrict__ saved,
+                                                               const float* __restrict__ w_hh,
+                                                               const int* __restrict__ lengths, float* dgi,
+                                                               float* dgh, int B, int T, int H) {
+  const int lane = threadIdx.x;
+  const int j = lane & 15;
+  const int grp = lane >> 4;
+  const int base = lane & 48;
+  const int b0 = blockIdx.x * 4;
+  const int b = b0 + grp;
+  const int rows = min(4, B - b0);
+  const bool row = b < B;
+  const bool act = row && j < H;
+  float cr[GRU_SMALL_MAX], cz[GRU_SMALL_MAX], cn[GRU_SMALL_MAX];
+#pragma unroll
+  for (int i = 0; i < GRU_SMALL_MAX; ++i) {
+    const bool ok = act && i < H;
+    cr[i] = ok ? w_hh[(size_t)i * H + j] : 0.f;
+    cz[i] = ok ? w_hh[(size_t)(H + i) * H + j] : 0.f;
+    cn[i] = ok ? w_hh[(size_t)(2 * H + i) * H + j] : 0.f;
+  }
+  int len = T;
+  if (row && lengths) len = min(max(lengths[b], 0), T);
+  const float dhn = (act && dh_n) ? dh_n[(size_t)b * H + j] : 0.f;
+  const size_t BTH = (size_t)B * T * H, rowT = (size_t)rows * T;
+  __amdgpu_buffer_rsrc_t rs[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) rs[p] = gru_rsrc(saved + p * BTH + (size_t)b0 * T * H, rowT * H * 4);
+  const __amdgpu_buffer_rsrc_t rout = gru_rsrc(out + (size_t)b0 * T * H, rowT * H * 4);
+  const __amdgpu_buffer_rsrc_t rd = gru_rsrc(dout ? dout + (size_t)b0 * T * H : nullptr, rowT * H * 4);
+  const __amdgpu_buffer_rsrc_t rgi = gru_rsrc(dgi + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
+  const __amdgpu_buffer_rsrc_t rgh = gru_rsrc(dgh + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
+  const unsigned obase = 4u * ((unsigned)grp * T * H + j), gbase = 4u * ((unsigned)grp * T * 3 * H + j);
+  auto ooff = [&](int t) { return (act && t >= 0 && t < T) ? obase + 4u * (unsigned)(t * H) : GRU_OOB; };
+  auto goff = [&](int t) { return (act && t >= 0 && t < T) ? gbase + 4u * (unsigned)(t * 3 * H) : GRU_OOB; };
+
+  // operands of one step: r, z, n, W_hn h + b_hn, h_{t-1}, dout
+  float cur[6][GRU_SMALL_CH], nxt[6][GRU_SMALL_CH];
+  float po[4][GRU_SMALL_CH];  // dr, dz, dn, dn * r of the previous chunk
+  auto load = [&](float (&v)[6][GRU_SMALL_CH], int t0) {
+#pragma unroll
+    for (int s = 0; s < GRU_SMALL_CH; ++s) {
+      const int t = t0 - s;
+      const unsigned o = ooff(t);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) v[p][s] = gru_bload(rs[p], o);
+      v[4][s] = gru_bload(rout, (t >= 1 && o != GRU_OOB) ? o - 4u * H : GRU_OOB);
+      v[5][s] = gru_bload(rd, o);
+    }
+  };
+  load(cur, T - 1);
+#pragma unroll
+  for (int s = 0; s < GRU_SMALL_CH; ++s) po[0][s] = po[1][s] = po[2][s] = po[3][s] = 0.f;
+  gru_wait_vm();
+  float dh_next = 0.f, z_next = 0.f;   // dL/dh_{t+1} and z_{t+1}
+  float pr = 0.f, pz = 0.f, pnh = 0.f;  // this lane's dgh of step t + 1
+  for (int t0 = T - 1; t0 >= 0; t0 -= GRU_SMALL_CH) {
+#pragma unroll
+    for (int s = 0; s < GRU_SMALL_CH; ++s) {
+      const unsigned o = goff(t0 + GRU_SMALL_CH - s);
+      gru_bstore(po[0][s], rgi, o);
+      gru_bstore(po[1][s], rgi, o + 4u * H);
+      gru_bstore(po[2][s], rgi, o + 8u * H);
+      gru_bstore(po[0][s], rgh, o);
+      gru_bstore(po[1][s], rgh, o + 4u * H);
+      gru_bstore(po[3][s], rgh, o + 8u * H);
+    }
+    load(nxt, t0 - GRU_SMALL_CH);
+#pragma unroll
+    for (int s = 0; s < GRU_SMALL_CH; ++s) {
+      const int t = t0 - s;
+      const float r = cur[0][s], z = cur[1][s], n = cur[2][s], hn = cur[3][s], hp = cur[4][s];
+      float rec = 0.f;
+      {
+        float gr[GRU_SMALL_MAX], gz[GRU_SMALL_MAX], gn[GRU_SMALL_MAX];
+#pragma unroll
+        for (int i = 0; i < GRU_SMALL_MAX; ++i) {
+          gr[i] = __shfl(pr, base + i, 64);
+          gz[i] = __shfl(pz, base + i, 64);
+          gn[i] = __shfl(pnh, base + i, 64);
+        }
+#pragma unroll
+        for (int i = 0; i < GRU_SMALL_MAX; ++i) rec += gr[i] * cr[i] + gz[i] * cz[i] + gn[i] * cn[i];
+      }
+      float dh = cur[5][s];
+      if (t == len - 1) dh += dhn;
+      if (t + 1 < T) dh += dh_next * z_next + rec;
+      if (t >= len) dh = 0.f;
+      const float dn_pre = dh * (1.f - z) * (1.f - n * n);
+      const float dz_pre = dh * (hp - n) * z * (1.f - z);
+      const float dr_pre = dn_pre * hn * r * (1.f - r);
+      po[0][s] = dr_pre, po[1][s] = dz_pre, po[2][s] = dn_pre, po[3][s] = dn_pre * r;
+      if (t >= 0) {
+        pr = act ? dr_pre : 0.f;
+        pz = act ? dz_pre : 0.f;
+        pnh = act ? dn_pre * r : 0.f;
+        dh_next = dh;
+        z_next = z;
+      }
+    }
+    gru_wait_vm();
+#pragma unroll
+    for (int s = 0; s < GRU_SMALL_CH; ++s)
+#pragma unroll
+      for (int p = 0; p < 6; ++p) cur[p][s] = nxt[p][s];
+  }
+  const int tlast = (T - 1) % GRU_SMALL_CH;  // the last chunk starts at step tlast and walks down to (past) 0
+#pragma unroll
+  for (int s = 0; s < GRU_SMALL_CH; ++s) {
+    const unsigned o = goff(tlast - s);
+    gru_bstore(po[0][s], rgi, o);
+    gru_bstore(po[1][s], rgi, o + 4u * H);
+    gru_bstore(po[2][s], rgi, o + 8u * H);
+    gru_bstore(po[0][s], rgh, o);
+    gru_bstore(po[1][s], rgh, o + 4u * H);
+    gru_bstore(po[3][s], rgh, o + 8u * H);
+  }
+}
+
+extern "C" {
+
+// the byte extent of every buffer a wave of the small kernels addresses (4 rows x T x 3H floats) stays below 2^30,
+// far from the range-check offset GRU_OOB
+static bool gru_small_fits(int T, int H) { return 4ull * (unsigned long long)T * 3ull * (unsigned long long)H * 4ull < (1ull << 30); }
+
+int m2d_gru_small_fwd(const float* gi, const float* w_hh, const float* b_hh, const int* lengths, float* out,
+                      float* h_n, float* saved, int B, int T, int H, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (H < 1 || H > GRU_SMALL_MAX) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_fwd: H = %d outside [1, 16]", H);
+  if (B <= 0 || T <= 0 || !gru_small_fits(T, H)) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_fwd: bad shape");
+  if (!gi || !w_hh || !b_hh || !h_n) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_fwd: gi, w_hh, b_hh and h_n are required");
+  M2dProfScope prof(M2D_FAM_GRU, stream, 2.0 * B * 3.0 * H * H * (double)T, 0.0, "gru_small_fwd", B, T, H);
+  hipLaunchKernelGGL(m2d_gru_small_fwd_kernel, dim3(m2d_ceil_div(B, 4)), dim3(64), 0, stream, gi, w_hh, b_hh,
+                     lengths, out, h_n, saved, B, T, H);
+  M2D_CHECK_LAUNCH("m2d_gru_small_fwd_kernel");
+  return M2D_OK;
+}
+
+int m2d_gru_small_bwd(const float* dout, const float* dh_n, const float* out, const float* saved, const float* w_hh,
+                      const int* lengths, float* dgi, float* dgh, int B, int T, int H, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (H < 1 || H > GRU_SMALL_MAX) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_bwd: H = %d outside [1, 16]", H);
+  if (B <= 0 || T <= 0 || !gru_small_fits(T, H)) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_bwd: bad shape");
+  if (!out || !saved || !w_hh || !dgi || !dgh)
+    M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_bwd: out, saved, w_hh, dgi and dgh are required");
+  M2dProfScope prof(M2D_FAM_GRU, stream, 2.0 * B * 3.0 * H * H * (double)T, 0.0, "gru_small_bwd", B, T, H);
+  hipLaunchKernelGGL(m2d_gru_small_bwd_kernel, dim3(m2d_ceil_div(B, 4)), dim3(64), 0, stream, dout, dh_n, out,
+                     saved, w_hh, lengths, dgi, dgh, B, T, H);
+  M2D_CHECK_LAUNCH("m2d_gru_small_bwd_kernel");
+  return M2D_OK;
+}
+
+}  // extern "C"

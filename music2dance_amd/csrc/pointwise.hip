@@ -30,6 +30,72 @@ __global__ void __launch_bounds__(256) m2d_finish_sum_kernel(const double* parti
   if (threadIdx.x == 0) out[0] = (float)(s * scale);
 }
 
+// ---------------------------------------------------------------- softmax cross-entropy
+// torch.nn.CrossEntropyLoss(reduction='mean') of the dance classifier (dance_classification/main.py:126-135):
+// one wave per row of (B, C) logits (C <= 1024: up to 16 classes per lane), max-subtracted log-sum-exp with
+// the exponentials summed in fp64, argmax with the first maximum winning ties (torch.argmax). Every reduction
+// has a fixed shape, so a row's loss - and the fp64 sum over rows in m2d_finish_sum_kernel - is bit-stable.
+#define CE_MAX_C 1024
+
+struct CeRow {
+  float m;   // row maximum
+  double s;  // sum of exp(x - m)
+  int arg;   // first index of the maximum
+};
+
+__device__ __forceinline__ CeRow ce_row(const float* x, int C, int lane) {
+  float m = -INFINITY;
+  int arg = 0x7fffffff;
+  for (int c = lane; c < C; c += 64) {
+    const float v = x[c];
+    if (v > m || (arg == 0x7fffffff && !(v < m))) m = v, arg = c;  // a lane's first element always seeds it
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off, 64);
+    const int oa = __shfl_xor(arg, off, 64);
+    if (om > m || (om == m && oa < arg)) m = om, arg = oa;
+  }
+  double s = 0.0;
+  for (int c = lane; c < C; c += 64) s += (double)expf(x[c] - m);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  return CeRow{m, s, arg};
+}
+
+__global__ void __launch_bounds__(256) m2d_ce_fwd_rows_kernel(const float* __restrict__ logits,
+                                                              const long long* __restrict__ labels,
+                                                              double* row_loss, long long* pred, int B, int C) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;  // whole waves leave together
+  const float* x = logits + (size_t)b * C;
+  const CeRow r = ce_row(x, C, lane);
+  if (lane == 0) {
+    const long long y = labels[b];
+    row_loss[b] = (y >= 0 && y < C) ? (double)r.m + log(r.s) - (double)x[y] : (double)NAN;
+    if (pred) pred[b] = r.arg;
+  }
+}
+
+__global__ void __launch_bounds__(256) m2d_ce_bwd_kernel(const float* __restrict__ logits,
+                                                         const long long* __restrict__ labels,
+                                                         const float* __restrict__ gout, float* dlogits, int B,
+                                                         int C) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* x = logits + (size_t)b * C;
+  const CeRow r = ce_row(x, C, lane);
+  const long long y = labels[b];
+  const bool ok = y >= 0 && y < C;
+  const float g = gout[0] / (float)B;
+  for (int c = lane; c < C; c += 64) {
+    const float p = (float)((double)expf(x[c] - r.m) / r.s);
+    dlogits[(size_t)b * C + c] = ok ? (p - (c == y ? 1.f : 0.f)) * g : NAN;
+  }
+}
+
 // ---------------------------------------------------------------- GP interpolate
 // out[b,i] = alpha[b] * real[b,i] + (1 - alpha[b]) * fake[b,i], three separately rounded
 // fp32 operations exactly like the reference expression (losses.py:20).
@@ -996,6 +1062,37 @@ int m2d_upsample2_bwd(const float* dy, float* dx, size_t rows, int L, void* stre
   else
     hipLaunchKernelGGL(m2d_upsample2_bwd_kernel, dim3(grid_for(rows * L, 4096)), dim3(256), 0, stream, dy, dx, rows, L);
   M2D_CHECK_LAUNCH("m2d_upsample2_bwd");
+  return M2D_OK;
+}
+
+size_t m2d_cross_entropy_workspace_bytes(int B, int C) {
+  (void)C;
+  return B > 0 ? (size_t)B * sizeof(double) : 0;
+}
+
+int m2d_cross_entropy_fwd(const float* logits, const long long* labels, float* loss, long long* pred, int B, int C,
+                          void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0 || C <= 0 || C > CE_MAX_C) M2D_FAIL(M2D_ERR_ARG, "m2d_cross_entropy_fwd: B = %d, C = %d (C <= 1024)", B, C);
+  if (!ws || ws_bytes < m2d_cross_entropy_workspace_bytes(B, C))
+    M2D_FAIL(M2D_ERR_WORKSPACE, "m2d_cross_entropy_fwd: workspace");
+  M2dProfScope prof(M2D_FAM_REDUCE, stream, 0.0, 4.0 * (double)B * C, "cross_entropy_fwd", B, C, 0);
+  hipLaunchKernelGGL(m2d_ce_fwd_rows_kernel, dim3(m2d_ceil_div(B, 4)), dim3(256), 0, stream, logits, labels,
+                     (double*)ws, pred, B, C);
+  hipLaunchKernelGGL(m2d_finish_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, B, 1.0 / (double)B,
+                     loss);
+  M2D_CHECK_LAUNCH("m2d_cross_entropy_fwd");
+  return M2D_OK;
+}
+
+int m2d_cross_entropy_bwd(const float* logits, const long long* labels, const float* gout, float* dlogits, int B,
+                          int C, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0 || C <= 0 || C > CE_MAX_C) M2D_FAIL(M2D_ERR_ARG, "m2d_cross_entropy_bwd: B = %d, C = %d (C <= 1024)", B, C);
+  M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 8.0 * (double)B * C, "cross_entropy_bwd", B, C, 0);
+  hipLaunchKernelGGL(m2d_ce_bwd_kernel, dim3(m2d_ceil_div(B, 4)), dim3(256), 0, stream, logits, labels, gout,
+                     dlogits, B, C);
+  M2D_CHECK_LAUNCH("m2d_cross_entropy_bwd");
   return M2D_OK;
 }
 

@@ -901,6 +901,46 @@ class HipKernels:
         return dgi, dgh
 
     @staticmethod
+    def _chk_lengths(lengths, dev, B):
+        """per-sequence lengths handed to a kernel: a contiguous int32 tensor of B entries on the kernels' device"""
+        if lengths is None:
+            return
+        if not lengths.is_cuda or lengths.device != dev or lengths.dtype != torch.int32 or not lengths.is_contiguous():
+            raise _lib.M2dError("GRU lengths must be a contiguous int32 tensor on %s (got %s %s)"
+                                % (dev, lengths.dtype, lengths.device))
+        if lengths.numel() != B:
+            raise _lib.M2dError("GRU lengths: %d entries for a batch of %d" % (lengths.numel(), B))
+
+    def gru_small_fwd(self, gi, w_hh, b_hh, lengths=None, save=True, with_out=True):
+        """One GRU layer with 1 <= H <= 16 in one launch. gi: (B, T, 3H) with b_ih added; w_hh: (3H, H).
+        Returns (out (B,T,H) or None, h_n (B,H), saved (4,B,T,H) or None); save implies out (the backward reads it)."""
+        dev = _chk(gi, w_hh, b_hh)
+        B, T, H3 = gi.shape
+        H = H3 // 3
+        self._chk_lengths(lengths, dev, B)
+        out = torch.empty((B, T, H), dtype=torch.float32, device=dev) if (with_out or save) else None
+        h_n = torch.empty((B, H), dtype=torch.float32, device=dev)
+        saved = torch.empty((4, B, T, H), dtype=torch.float32, device=dev) if save else None
+        with _on(dev):
+            rc = _lib.lib().m2d_gru_small_fwd(_ptr(gi), _ptr(w_hh), _ptr(b_hh), _ptr(lengths), _ptr(out), _ptr(h_n),
+                                              _ptr(saved), B, T, H, _stream(dev))
+        _lib.check(rc, "m2d_gru_small_fwd")
+        return out, h_n, saved
+
+    def gru_small_bwd(self, dout, dh_n, out, saved, w_hh, lengths=None):
+        """BPTT of gru_small_fwd (dout and / or dh_n may be None) -> (dgi, dgh), each (B, T, 3H)."""
+        dev = _chk(dout, dh_n, out, saved, w_hh)
+        B, T, H = out.shape
+        self._chk_lengths(lengths, dev, B)
+        dgi = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
+        dgh = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
+        with _on(dev):
+            rc = _lib.lib().m2d_gru_small_bwd(_ptr(dout), _ptr(dh_n), _ptr(out), _ptr(saved), _ptr(w_hh),
+                                              _ptr(lengths), _ptr(dgi), _ptr(dgh), B, T, H, _stream(dev))
+        _lib.check(rc, "m2d_gru_small_bwd")
+        return dgi, dgh
+
+    @staticmethod
     def _ptr_array(tensors):
         arr = (ctypes.c_void_p * len(tensors))(*[_ptr(t) for t in tensors])
         return arr, ctypes.cast(arr, ctypes.c_void_p)
@@ -1044,6 +1084,38 @@ class HipKernels:
             rc = _lib.lib().m2d_l1_mean_bwd(_ptr(a), _ptr(b), _ptr(gout), _ptr(da), a.numel(), _stream(dev))
         _lib.check(rc, "m2d_l1_mean_bwd")
         return da
+
+    @staticmethod
+    def _chk_labels(labels, dev, B):
+        if not labels.is_cuda or labels.device != dev or labels.dtype != torch.int64 or not labels.is_contiguous():
+            raise _lib.M2dError("cross entropy: labels must be a contiguous int64 tensor on %s" % dev)
+        if labels.numel() != B:
+            raise _lib.M2dError("cross entropy: %d labels for %d rows" % (labels.numel(), B))
+
+    def cross_entropy_fwd(self, logits, labels, with_pred=False):
+        """mean softmax cross-entropy of (B, C) logits against int64 labels -> (0-dim loss, int64 argmax or None)"""
+        dev = _chk(logits)
+        B, C = logits.shape
+        self._chk_labels(labels, dev, B)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        pred = torch.empty((B,), dtype=torch.int64, device=dev) if with_pred else None
+        ws = _ws(_ws_bytes('m2d_cross_entropy_workspace_bytes', B, C), dev)
+        with _on(dev):
+            rc = _lib.lib().m2d_cross_entropy_fwd(_ptr(logits), _ptr(labels), _ptr(loss), _ptr(pred), B, C, _ptr(ws),
+                                                  0 if ws is None else ws.numel() * 4, _stream(dev))
+        _lib.check(rc, "m2d_cross_entropy_fwd")
+        return loss, pred
+
+    def cross_entropy_bwd(self, logits, labels, gout):
+        dev = _chk(logits, gout)
+        B, C = logits.shape
+        self._chk_labels(labels, dev, B)
+        dlogits = torch.empty_like(logits)
+        with _on(dev):
+            rc = _lib.lib().m2d_cross_entropy_bwd(_ptr(logits), _ptr(labels), _ptr(gout), _ptr(dlogits), B, C,
+                                                  _stream(dev))
+        _lib.check(rc, "m2d_cross_entropy_bwd")
+        return dlogits
 
     def tv_mean_fwd(self, x, B, C, T, sb, sc, st):
         """x: storage holding a (B, C, T) view with element strides (sb, sc, st)."""

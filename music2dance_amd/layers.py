@@ -178,6 +178,16 @@ class GRU(nn.GRU):
             out = ops.gru_layer(out, *params[4 * layer:4 * layer + 4], lengths)
         return out, None
 
+    def final_state(self, x, lengths=None):
+        """h_n[-1] (B, H) of a single-layer GRU: what `self.rnn(x)[1].squeeze(0)` reads in the reference's dance
+        classifier (dance_classification/archis/default.py:24-25). Hidden sizes <= 16 run on the small-state
+        kernels (ops.gru_final_state)."""
+        if not self.batch_first or self.bidirectional or self.dropout != 0.0 or not self.bias:
+            raise NotImplementedError("m2d GRU: only batch_first / unidirectional / no-dropout is supported")
+        if self.num_layers != 1:
+            raise NotImplementedError("m2d GRU.final_state: single-layer GRUs only")
+        return ops.gru_final_state(x, self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0, lengths)
+
 
 class WindowView:
     """(B, T, window) audio windows as a view of the padded track (B, S): window t of track b is

@@ -62,3 +62,9 @@ def jerkiness(sequence):
     """Evaluation metric of the reference (losses.py:85-89, phase3/test.py:78-104): the squared third finite
     difference along time of a (B, C, T) sequence, summed over channels, averaged over (B, T - 3)."""
     return ops.jerk_mean(sequence)
+
+
+def cross_entropy(logits, target):
+    """torch.nn.CrossEntropyLoss(reduction='mean') of the dance classifier (dance_classification/main.py:126) on the
+    HIP kernels: logits (B, C), int64 class indices (B,)."""
+    return ops.cross_entropy(logits, target)

@@ -570,6 +570,22 @@ def batch_norm(x, gamma, beta, running_mean, running_var, training, eps=1e-5, mo
 
 
 # --------------------------------------------------------------------------------------- GRU
+def _gru_layer_grads(x, w_ih, out, dgi, dgh, need_dx):
+    """(dx or None, dW_ih, dW_hh, db_ih, db_hh) of one GRU layer from the pre-activation gradients dgi / dgh (B, T, 3H)
+    its BPTT kernel wrote: engine GEMMs over all T steps and channel sums."""
+    B, T, I = x.shape
+    H = out.shape[2]
+    k = K()
+    dgi2, dgh2 = dgi.view(B * T, 3 * H), dgh.view(B * T, 3 * H)
+    dx = k.gemm(1, dgi2, w_ih).view(B, T, I) if need_dx else None
+    dw_ih = k.gemm(2, dgi2, x.view(B * T, I))
+    hprev = torch.cat((out.new_zeros(B, 1, H), out[:, :-1]), 1).contiguous().view(B * T, H)
+    dw_hh = k.gemm(2, dgh2, hprev)
+    db_ih = k.channel_sums(dgi2.view(B * T, 3 * H, 1))
+    db_hh = k.channel_sums(dgh2.view(B * T, 3 * H, 1))
+    return dx, dw_ih, dw_hh, db_ih, db_hh
+
+
 class _GRULayer(Function):
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, lengths, save):
@@ -590,18 +606,8 @@ class _GRULayer(Function):
         if dout is None:  # no gradient reaches this node (e.g. the penalty pass's forward graph)
             return (None,) * 7
         x, w_ih, w_hh, out, saved, lengths = ctx.saved_tensors
-        B, T, I = x.shape
-        H = w_hh.shape[1]
-        k = K()
-        dgi, dgh = k.gru_layer_bwd(_c(dout), out, saved, w_hh, lengths)
-        dgi2, dgh2 = dgi.view(B * T, 3 * H), dgh.view(B * T, 3 * H)
-        dx = k.gemm(1, dgi2, w_ih).view(B, T, I) if ctx.needs_input_grad[0] else None
-        dw_ih = k.gemm(2, dgi2, x.view(B * T, I))
-        hprev = torch.cat((out.new_zeros(B, 1, H), out[:, :-1]), 1).contiguous().view(B * T, H)
-        dw_hh = k.gemm(2, dgh2, hprev)
-        db_ih = k.channel_sums(dgi2.view(B * T, 3 * H, 1))
-        db_hh = k.channel_sums(dgh2.view(B * T, 3 * H, 1))
-        return dx, dw_ih, dw_hh, db_ih, db_hh, None, None
+        dgi, dgh = K().gru_layer_bwd(_c(dout), out, saved, w_hh, lengths)
+        return _gru_layer_grads(x, w_ih, out, dgi, dgh, ctx.needs_input_grad[0]) + (None, None)
 
 
 class _GRUStack(Function):
@@ -663,6 +669,60 @@ def gru_layer(x, w_ih, w_hh, b_ih, b_hh, lengths=None):
     """One nn.GRU layer (batch_first, h0 = 0) over a whole (B, T, in) sequence."""
     save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, w_ih, w_hh, b_ih, b_hh))
     return _GRULayer.apply(x, w_ih, w_hh, b_ih, b_hh, lengths, save)
+
+
+GRU_SMALL_MAX = 16  # widest hidden size of m2d_gru_small_fwd / _bwd
+
+
+def _gru_small_enabled():
+    """M2D_GRU_SMALL=0 sends every gru_final_state through gru_stack + a gather (A/B lever); read per call"""
+    return os.environ.get("M2D_GRU_SMALL", "1") != "0"
+
+
+class _GRUFinal(Function):
+    """h_n of one GRU layer with H <= 16: the small-state kernels, the whole sequence in one launch each way."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, lengths, save):
+        ctx.set_materialize_grads(False)
+        x, w_ih, w_hh, b_ih, b_hh = _c(x), _c(w_ih), _c(w_hh), _c(b_ih), _c(b_hh)
+        B, T, I = x.shape
+        H = w_hh.shape[1]
+        k = K()
+        gi = k.gemm(0, x.view(B * T, I), w_ih, b_ih).view(B, T, 3 * H)
+        out, h_n, saved = k.gru_small_fwd(gi, w_hh, b_hh, lengths, save=save, with_out=False)
+        if save:
+            ctx.save_for_backward(x, w_ih, w_hh, out, saved, lengths)
+        return h_n
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dh_n):
+        if dh_n is None:
+            return (None,) * 7
+        x, w_ih, w_hh, out, saved, lengths = ctx.saved_tensors
+        dgi, dgh = K().gru_small_bwd(None, _c(dh_n), out, saved, w_hh, lengths)
+        return _gru_layer_grads(x, w_ih, out, dgi, dgh, ctx.needs_input_grad[0]) + (None, None)
+
+
+def gru_final_state(x, w_ih, w_hh, b_ih, b_hh, lengths=None):
+    """h_n (B, H) of one nn.GRU layer (batch_first, h0 = 0) over (B, T, in): the state after step lengths[b] - 1
+    (T - 1 without lengths). H <= 16 runs on the small-state kernels; wider states (or M2D_GRU_SMALL=0) run
+    gru_stack and gather the last valid step. `lengths`: any integer tensor or sequence of B entries (the CPU int64
+    lengths pack_padded_sequence takes included); it is moved to the device as int32."""
+    H = w_hh.shape[1]
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).contiguous()
+        if lengths.numel() != x.shape[0]:
+            raise ValueError("gru_final_state: %d lengths for a batch of %d" % (lengths.numel(), x.shape[0]))
+    if H <= GRU_SMALL_MAX and _gru_small_enabled():
+        save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, w_ih, w_hh, b_ih, b_hh))
+        return _GRUFinal.apply(x, w_ih, w_hh, b_ih, b_hh, lengths, save)
+    out = gru_stack(x, [w_ih, w_hh, b_ih, b_hh], lengths)
+    if lengths is None:
+        return out[:, -1]
+    last = (lengths.to(device=out.device, dtype=torch.long) - 1).clamp(0, out.shape[1] - 1)
+    return out[torch.arange(out.shape[0], device=out.device), last]
 
 
 # --------------------------------------------------------------------------------------- GP
@@ -736,6 +796,38 @@ class _TVMean(Function):
             return (None,) * 7
         (store,) = ctx.saved_tensors
         return (K().tv_mean_bwd(store, _c(gout), *ctx.cfg),) + (None,) * 6
+
+
+class _CrossEntropy(Function):
+    @staticmethod
+    def forward(ctx, logits, target):
+        ctx.set_materialize_grads(False)
+        logits = _c(logits)
+        loss, _ = K().cross_entropy_fwd(logits, target)
+        ctx.save_for_backward(logits, target)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None
+        logits, target = ctx.saved_tensors
+        return K().cross_entropy_bwd(logits, target, _c(gout)), None
+
+
+def cross_entropy(logits, target):
+    """torch.nn.CrossEntropyLoss(reduction='mean')(logits (B, C), target int64 (B,)), C <= 1024."""
+    target = target.reshape(-1)
+    if target.dtype != torch.int64 or not target.is_contiguous():
+        target = target.to(torch.int64).contiguous()
+    return _CrossEntropy.apply(logits, target)
+
+
+def cross_entropy_pred(logits, target):
+    """(loss, argmax of each row) from one launch pair, no graph: the evaluation form."""
+    target = target.reshape(-1).to(torch.int64).contiguous()
+    return K().cross_entropy_fwd(_c(logits.detach()), target, with_pred=True)
 
 
 def tv_mean(seq):

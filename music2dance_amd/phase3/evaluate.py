@@ -1,0 +1,193 @@
+"""Score a trained phase-3 generator as the reference's phase3/test.py:76-140 does, on the HIP path.
+
+    python -m music2dance_amd.phase3.evaluate -c music2dance_amd/phase3/configs/default.yaml -l <logdir> \
+        --classifier logs/type2/weights.pt [--gen-weights PATH] [--repeats 20] [--synthetic]
+
+1. Jerkiness (losses.jerkiness) of every real validation take and of the dance generated from its music, on
+   inverse-MinMax-scaled poses: mean and unbiased standard deviation of each.
+2. Style consistency: the dance-style classifier (dance_classification.archis.default.RecurrentDanceClassifier, eval
+   mode) labels each real take and its generated counterpart; the confusion matrix of real-predicted (rows) against
+   fake-predicted (columns) labels, row-normalised. It is always C x C, a row without samples is NaN (sklearn's matrix
+   shrinks to the labels present instead).
+
+The validation takes are <logdir>/trainvaltest_samples.json's `val_samples`, each drawn `--repeats` times (a fresh
+random crop per draw, as the reference's loader makes); all draws go through ONE eval-mode generator call (eval-mode
+BatchNorm keeps the rows independent, so only the order of the noise draws differs from the reference's batch-1 loop).
+The generator checkpoint defaults to the latest <logdir>/models/gpgen_*.pt. Writes <logdir>/evaluation.json, strict
+JSON: an undefined value (a confusion row without samples, the spread of a single sequence) is `null`.
+"""
+import argparse
+import glob
+import json
+import os
+import re
+
+import numpy as np
+import torch
+
+from .. import losses, ops, runner
+from ..dance_classification.archis.default import RecurrentDanceClassifier
+from .archis.default import SequenceGenerator
+
+N_STYLES = 4
+STICK_CHANNELS = 69
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("-c", "--config", type=str, required=True, help="phase-3 config file of the generator")
+    ap.add_argument("-l", "--logdir", type=str, required=True, help="run directory of the generator")
+    ap.add_argument("--gen-weights", type=str, default=None, help="generator state_dict (default: latest "
+                                                                    "<logdir>/models/gpgen_*.pt)")
+    ap.add_argument("--classifier", type=str, required=True, help="RecurrentDanceClassifier state_dict")
+    ap.add_argument("--repeats", type=int, default=20, help="draws of every validation take")
+    ap.add_argument("--synthetic", action="store_true", help="random poses / audio / styles of the dataset's shapes")
+    ap.add_argument("--folder", type=str, default=None, help="dataset folder (overrides the YAML's `folder:`)")
+    ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
+    return ap.parse_args(argv)
+
+
+def latest_checkpoint(logdir):
+    """<logdir>/models/gpgen_<iteration>.pt with the largest iteration, or None"""
+    best, best_it = None, -1
+    for p in glob.glob(os.path.join(logdir, "models", "gpgen_*.pt")):
+        m = re.search(r"gpgen_(\d+)\.pt$", p)
+        if m and int(m.group(1)) > best_it:
+            best, best_it = p, int(m.group(1))
+    return best
+
+
+def confusion(real_pred, fake_pred, n_classes=N_STYLES):
+    """-> (row-normalised C x C matrix of real-predicted (row) vs fake-predicted (column) labels, NaN rows where a
+    real label never occurs; the raw counts)."""
+    real_pred = np.asarray(real_pred, dtype=np.int64).reshape(-1)
+    fake_pred = np.asarray(fake_pred, dtype=np.int64).reshape(-1)
+    counts = np.zeros((n_classes, n_classes), dtype=np.int64)
+    np.add.at(counts, (real_pred, fake_pred), 1)
+    rows = counts.sum(axis=1, keepdims=True).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cm = np.where(rows > 0, counts / np.where(rows > 0, rows, 1.0), np.nan)
+    return cm, counts
+
+
+def jerk_stats(values):
+    """(mean, unbiased standard deviation) of per-sequence jerkiness values (torch.std's default; NaN for one value)"""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    return float(v.mean()), (float(v.std(ddof=1)) if v.size > 1 else float("nan"))
+
+
+def summary(real_jerk, fake_jerk, real_pred, fake_pred, n_classes=N_STYLES):
+    cm, counts = confusion(real_pred, fake_pred, n_classes)
+    rm, rs = jerk_stats(real_jerk)
+    fm, fs = jerk_stats(fake_jerk)
+    total = int(counts.sum())
+    return {"jerk_real_mean": rm, "jerk_real_std": rs, "jerk_fake_mean": fm, "jerk_fake_std": fs,
+            "confusion": cm.tolist(), "style_agreement": float(np.trace(counts)) / total if total else float("nan"),
+            "n_sequences": total}
+
+
+def json_safe(v):
+    """NaN / inf -> None (JSON null), recursively through lists and dicts"""
+    if isinstance(v, dict):
+        return {k: json_safe(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [json_safe(x) for x in v]
+    if isinstance(v, float) and not np.isfinite(v):
+        return None
+    return v
+
+
+def build_generator(cfg, device):
+    rate = cfg["dataset"]["audio_rate"]
+    return SequenceGenerator(int(cfg["window_size"] * rate), cfg["input_vector_size"], cfg["latent_vector_size"],
+                             cfg["size"], cfg["output_size"], cfg["noise_size"], cfg["nblocks_gen"], cfg["n_cells"],
+                             cfg["enc_type"], cfg["activ"], device)
+
+
+def _takes(opts, cfg, device):
+    """-> (real poses (N, T, 69), audio tracks (N, S), labels (N,), scaler, window, hop): the validation takes,
+    each drawn `repeats` times."""
+    from .. import data as D
+    ds = cfg["dataset"]
+    window = int(cfg["window_size"] * ds["audio_rate"])
+    hop = int(ds["audio_rate"] // ds["video_rate"])
+    split = os.path.join(opts.logdir, "trainvaltest_samples.json")
+    if opts.synthetic:
+        n_val = 6
+        if os.path.exists(split):
+            with open(split) as f:
+                n_val = max(len(json.load(f).get("val_samples", [])), 1)
+        from ..engine import synthetic_phase3_batch
+        T = int(ds["seq_length"] * ds["video_rate"])
+        real, audio, _ = synthetic_phase3_batch(n_val * opts.repeats, T, device, seed=12345,
+                                                audio_rate=ds["audio_rate"], video_rate=ds["video_rate"],
+                                                window_s=cfg["window_size"])
+        g = torch.Generator(device=device).manual_seed(12346)
+        labels = torch.randint(0, N_STYLES, (n_val,), generator=g, device=device).repeat(opts.repeats)
+        scaler = D.MinMaxScaler().fit(real.reshape(-1, STICK_CHANNELS).cpu().numpy())
+        return real, audio, labels, scaler, window, hop
+    with open(split) as f:
+        val_dirs = json.load(f)["val_samples"]
+    folder = runner.dataset_folder(cfg, opts.folder)
+    sticks = D.StickDataset(folder, normalize="minmax")
+    dataset = D.SequenceDataset(folder, ds, dance_types=cfg["dance_types"], scaler=sticks.scaler, withaudio=True)
+    dataset.truncate()
+    where = {d: i for i, d in enumerate(dataset.dirs)}
+    missing = [d for d in val_dirs if d not in where]
+    if missing:
+        raise SystemExit("validation takes not in the dataset: %s" % missing[:5])
+    idx = [where[d] for d in val_dirs]
+    parts = [dataset.sample_batch(idx, device) for _ in range(opts.repeats)]
+    real = torch.cat([p[0].reshape(len(idx), dataset.stick_length, STICK_CHANNELS) for p in parts]).float()
+    audio = torch.cat([p[2] for p in parts]).float()
+    labels = torch.cat([p[3].reshape(-1) for p in parts]).long()
+    return real, audio, labels, sticks.scaler, int(cfg["window_size"] * dataset.aud_rate), dataset.ratio
+
+
+@torch.no_grad()
+def evaluate(opts, cfg, device):
+    from ..utils import slice_audio_batch
+    gen = build_generator(cfg, device)
+    path = opts.gen_weights or latest_checkpoint(opts.logdir)
+    if path is not None:
+        gen.load_state_dict(torch.load(path, map_location=device))
+    elif not opts.synthetic:
+        raise SystemExit("no generator checkpoint: pass --gen-weights or train into %s/models" % opts.logdir)
+    classifier = RecurrentDanceClassifier(STICK_CHANNELS, 128, N_STYLES).to(device)
+    classifier.load_state_dict(torch.load(opts.classifier, map_location=device))
+    gen.eval(), classifier.eval()
+
+    real, audio, labels, scaler, window, hop = _takes(opts, cfg, device)
+    N, T, _ = real.shape
+    real = real.contiguous()
+    slices = slice_audio_batch(audio.contiguous(), window, hop, window - hop, lazy=True)
+    fake = gen(slices, [T] * N).reshape(N, T, STICK_CHANNELS)
+
+    # jerkiness per sequence on the inverse-scaled poses (phase3/test.py:76-104)
+    real_i = scaler.inverse_transform_device(real)
+    fake_i = scaler.inverse_transform_device(fake.contiguous())
+    real_jerk = torch.stack([losses.jerkiness(real_i[i:i + 1].permute(0, 2, 1)) for i in range(N)])
+    fake_jerk = torch.stack([losses.jerkiness(fake_i[i:i + 1].permute(0, 2, 1)) for i in range(N)])
+
+    # style classification of every real take and its generated counterpart (phase3/test.py:107-140)
+    _, real_pred = ops.cross_entropy_pred(classifier(real.permute(0, 2, 1).contiguous()), labels)
+    _, fake_pred = ops.cross_entropy_pred(classifier(fake.permute(0, 2, 1).contiguous()), labels)
+    return summary(real_jerk.cpu().numpy(), fake_jerk.cpu().numpy(), real_pred.cpu().numpy(),
+                   fake_pred.cpu().numpy())
+
+
+def main(argv=None):
+    opts = parse_args(argv)
+    cfg = runner.load_config(opts.config)
+    device = runner.pick_device(opts.device)
+    os.makedirs(opts.logdir, exist_ok=True)
+    torch.manual_seed(0)
+    res = evaluate(opts, cfg, device)
+    with open(os.path.join(opts.logdir, "evaluation.json"), "w") as f:
+        json.dump(json_safe(res), f, indent=1, allow_nan=False)
+    print(json.dumps(json_safe(res), allow_nan=False))
+    return res
+
+
+if __name__ == "__main__":
+    main()
