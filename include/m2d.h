@@ -317,6 +317,18 @@ int m2d_cross_entropy_fwd(const float* logits, const long long* labels, float* l
 int m2d_cross_entropy_bwd(const float* logits, const long long* labels, const float* gout, float* dlogits, int B,
                           int C, void* stream);
 
+/* ---- binary cross-entropy on logits (torch.nn.BCEWithLogitsLoss, mean; phase2/train.py:204-240, `-f gan`) --------
+ * BCEWithLogitsLoss(reduction='mean') per segment: x = (n0 + n1) logits, segment 0 against target t0, segment 1
+ * (n1 may be 0) against t1. out[0] = mean_0 + mean_1, out[1] = mean_0, out[2] = mean_1 (0 when n1 == 0).
+ * dx (optional, NULL = not written) = d out[0] / dx = (sigmoid(x) - t) / n_segment.
+ * Elements as torch computes them, max(x, 0) - x t + log1p(exp(-|x|)), in fp64; each segment summed in fp64 in a
+ * fixed order by one workgroup (bit-stable from run to run). A NaN logit gives a NaN loss and gradient.
+ * n0 <= 0 or n1 < 0: M2D_ERR_ARG. */
+int m2d_bce_logits_fwd(const float* x, int n0, float t0, int n1, float t1, float* out, float* dx, void* stream);
+/* dx = gout[0] * (sigmoid(x) - t) / n_segment, gout a device scalar */
+int m2d_bce_logits_bwd(const float* x, int n0, float t0, int n1, float t1, const float* gout, float* dx,
+                       void* stream);
+
 /* ---- gradient penalty (losses.py:5-60) ----------------------------------------------------- */
 int m2d_gp_interpolate(const float* real, const float* fake, const float* alpha, float* out, int B, int n,
                        void* stream);

@@ -135,6 +135,76 @@ class CriticStep:
                 return self.ctx.__exit__(*exc)
             return False
 
+    # ------------------------------------------------------------------ pose-branch sections (shared with GanCriticStep)
+    def _pose_forward(self, X, fw, rows):
+        """forward of the pose branch over rows `fw` of X (R, C, T) -> (a, p, q): per block its input a[i], first
+        conv's output p[i] and second conv's output q[i] (the activation masks), a[-1] the branch's output; each
+        (R, CH, T) from rows(CH), written on rows `fw`"""
+        k = K()
+        w1, b1, _, pad1 = _conv_params(self.stick.conv1)
+        CH = w1.shape[0]
+        a = [rows(CH)]
+        k.conv1d_fwd(X[fw], w1, b1, 1, pad1, ACT_RELU, out=a[0][fw])
+        p, q = [], []
+        for blk in self.stick.blocks:
+            wa, ba, _, pa = _conv_params(blk.conv1)
+            wb, bb, _, pb = _conv_params(blk.conv2)
+            pk, qk, ak = rows(CH), rows(CH), rows(CH)
+            k.conv1d_fwd(a[-1][fw], wa, ba, 1, pa, ACT_RELU, out=pk[fw])
+            k.conv1d_fwd(pk[fw], wb, bb, 1, pb, ACT_RELU, residual=a[-1][fw], out=qk[fw], sum_out=ak[fw])
+            p.append(pk)
+            q.append(qk)
+            a.append(ak)
+        return a, p, q
+
+    def _pose_backward_data(self, de_s, a, p, q, rows):
+        """backward-data chain of the pose branch for the (R, Cc) cotangents de_s at the full-length conv's output ->
+        (da, dp): the gradients at every block input (da[0]: after conv1's ReLU) and at every block's first conv"""
+        k = K()
+        st = self.stick
+        nb = len(st.blocks)
+        R, CH, T = a[0].shape
+        fw2d = self.fconv.weight.view(self.fconv.weight.shape[0], CH * T)
+        da = [rows(CH) for _ in range(nb + 1)]
+        dp = [rows(CH) for _ in range(nb)]
+        k.gemm(1, de_s, fw2d, out=da[nb].view(R, CH * T))
+        for i in range(nb - 1, -1, -1):
+            blk = st.blocks[i]
+            wa, _, _, pa = _conv_params(blk.conv1)
+            wb, _, _, pb = _conv_params(blk.conv2)
+            k.conv1d_bwd_data(da[i + 1], wb, T, 1, pb, dy_mask=q[i], out_mask=p[i], out=dp[i])
+            k.conv1d_bwd_data(dp[i], wa, T, 1, pa, residual=da[i + 1], out_mask=a[0] if i == 0 else None, out=da[i])
+        if nb == 0:
+            da[0] = da[0] * (a[0] > 0)
+        return da, dp
+
+    def _pose_weight_grads(self, c, a, p, q, da, dp, X, b0, put, ready):
+        """weight gradients of the pose branch, one launch per layer over all R rows, in reverse parameter order: c (R, Cc)
+        the cotangents at the full-length conv's output. Bias gradients sum rows [b0, R) only (rows in front pair
+        second-order operands). put(conv, dW, db, defer) binds them; ready (or None) after each layer's."""
+        k = K()
+        st = self.stick
+        nb = len(st.blocks)
+        R, CH, T = a[0].shape
+        w1, _, _, pad1 = _conv_params(st.conv1)
+        defer = ready is None
+        put(self.fconv, k.gemm(2, c, a[nb].view(R, CH * T)).view(self.fconv.weight.shape),
+            k.channel_sums(c[b0:].contiguous()), defer=defer)
+        if ready is not None:
+            ready()
+        for i in range(nb - 1, -1, -1):
+            blk = st.blocks[i]
+            wa, _, _, pa = _conv_params(blk.conv1)
+            wb, _, _, pb = _conv_params(blk.conv2)
+            put(blk.conv2, *k.conv1d_bwd_weight(p[i], da[i + 1], wb.shape[2], 1, pb, dy_mask=q[i], with_bias=True,
+                                                bias_from_sample=b0), defer=defer)
+            put(blk.conv1, *k.conv1d_bwd_weight(a[i], dp[i], wa.shape[2], 1, pa, with_bias=True,
+                                                bias_from_sample=b0), defer=defer)
+            if ready is not None:
+                ready()
+        put(st.conv1, *k.conv1d_bwd_weight(X, da[0], w1.shape[2], 1, pad1, with_bias=True, bias_from_sample=b0),
+            defer=defer)
+
     # ------------------------------------------------------------------ the pass
     @torch.no_grad()
     def run(self, real, fake_rows, audio=None, alpha=None, on_grads=None, fake_ready=None):
@@ -165,7 +235,7 @@ class CriticStep:
         c1, cw, gamma_t = self._constants(B, dev, dt)
         dbg = self.debug
         nb = len(st.blocks)
-        w1, b1, _, pad1 = _conv_params(st.conv1)
+        w1, _, _, pad1 = _conv_params(st.conv1)
         CH = w1.shape[0]
         Cc = self.fconv.weight.shape[0]
         fw2d = self.fconv.weight.view(Cc, CH * T)
@@ -186,18 +256,7 @@ class CriticStep:
         with self._On(side):
             X = torch.empty((R, C, T), dtype=dt, device=dev)
             k.pose_pack3(real.reshape(B, T, C), fake_rows, alpha.reshape(B), out=X[fw])
-            a = [rows(CH)]
-            k.conv1d_fwd(X[fw], w1, b1, 1, pad1, ACT_RELU, out=a[0][fw])
-            p, q = [], []
-            for blk in st.blocks:
-                wa, ba, _, pa = _conv_params(blk.conv1)
-                wb, bb, _, pb = _conv_params(blk.conv2)
-                pk, qk, ak = rows(CH), rows(CH), rows(CH)
-                k.conv1d_fwd(a[-1][fw], wa, ba, 1, pa, ACT_RELU, out=pk[fw])
-                k.conv1d_fwd(pk[fw], wb, bb, 1, pb, ACT_RELU, residual=a[-1][fw], out=qk[fw], sum_out=ak[fw])
-                p.append(pk)
-                q.append(qk)
-                a.append(ak)
+            a, p, q = self._pose_forward(X, fw, rows)
             if tanh:
                 # the activation masks of the interpolated rows, once more in the tangent block: the first backward then
                 # runs as one launch per layer over all 4B rows with row-aligned masks (the tangent pass overwrites
@@ -268,17 +327,7 @@ class CriticStep:
         # ---------------------------------------------------------------- backward-data chains
         side, cur = self._fork(dev)
         with self._On(side):
-            da = [rows(CH) for _ in range(nb + 1)]
-            dp = [rows(CH) for _ in range(nb)]
-            k.gemm(1, de_s, fw2d, out=da[nb].view(R, CH * T))
-            for i in range(nb - 1, -1, -1):
-                blk = st.blocks[i]
-                wa, _, _, pa = _conv_params(blk.conv1)
-                wb, _, _, pb = _conv_params(blk.conv2)
-                k.conv1d_bwd_data(da[i + 1], wb, T, 1, pb, dy_mask=q[i], out_mask=p[i], out=dp[i])
-                k.conv1d_bwd_data(dp[i], wa, T, 1, pa, residual=da[i + 1], out_mask=a[0] if i == 0 else None, out=da[i])
-            if nb == 0:
-                da[0] = da[0] * (a[0] > 0)
+            da, dp = self._pose_backward_data(de_s, a, p, q, rows)
             v_pose = k.conv1d_bwd_data(da[0][0:B], w1, T, 1, pad1)
             pen_p, norms_p = k.gp_penalty_fwd(v_pose.view(B, -1), self.lp)
         v_audio = pen_a = None
@@ -397,27 +446,9 @@ class CriticStep:
 
         side, cur = self._fork(dev)
         with self._On(side):
-            if self.has_head:
-                put(self.fconv, k.gemm(2, de_s, a[nb].view(R, CH * T)).view(self.fconv.weight.shape),
-                    k.channel_sums(de_s[B:].contiguous()), defer=side is not None)
-            else:
-                # phase 2: the full-length conv IS the score; its rows pair (tangent, 1) / (activation, +-1/B)
-                put(self.fconv, k.gemm(2, c1, a[nb].view(R, CH * T)).view(self.fconv.weight.shape),
-                    k.channel_sums(c1[B:].contiguous()), defer=side is not None)
-            if side is None:
-                ready()
-            for i in range(nb - 1, -1, -1):
-                blk = st.blocks[i]
-                wa, _, _, pa = _conv_params(blk.conv1)
-                wb, _, _, pb = _conv_params(blk.conv2)
-                put(blk.conv2, *k.conv1d_bwd_weight(p[i], da[i + 1], wb.shape[2], 1, pb, dy_mask=q[i], with_bias=True,
-                                                    bias_from_sample=B), defer=side is not None)
-                put(blk.conv1, *k.conv1d_bwd_weight(a[i], dp[i], wa.shape[2], 1, pa, with_bias=True,
-                                                    bias_from_sample=B), defer=side is not None)
-                if side is None:
-                    ready()
-            put(st.conv1, *k.conv1d_bwd_weight(X, da[0], w1.shape[2], 1, pad1, with_bias=True, bias_from_sample=B),
-                defer=side is not None)
+            # (phase 2: the full-length conv IS the score; its rows pair (tangent, 1) / (activation, +-1/B))
+            self._pose_weight_grads(de_s if self.has_head else c1, a, p, q, da, dp, X, B, put,
+                                    ready if side is None else None)
         if self.has_head:
             put(fc2, k.gemm(2, cw, z), k.channel_sums(cw[B:].contiguous()))
             put(fc1, k.gemm(2, dzp, e), k.channel_sums(dzp[B:].contiguous()))
@@ -439,3 +470,58 @@ class CriticStep:
             conv.weight.grad, conv.bias.grad = gw, gb
         ready()
         return {"loss_critic": losses[0], "gp": losses[1], "w_dist": losses[2]}
+
+
+class GanCriticStep(CriticStep):
+    """The critic iteration of the phase-2 `gan` framework (phase2/train.py:214-220) as one hand-scheduled pass:
+    err_critic = BCE(critic(real), 1) + BCE(critic(fake), 0), no penalty, so no interpolated rows and no tangent.
+
+      forward        pose branch ONCE over 2B rows [real | fake], channels-first; the full-length conv gives the 2B
+                     scores (the phase-2 critic has no BatchNorm and no dropout: one pass equals two calls).
+      loss           m2d_bce_logits_fwd writes the loss scalars AND the 2B score cotangents (sigmoid(s) - t) / B.
+      backward-data  the chain of CriticStep over the 2B rows.
+      weight grads   one launch per layer over the 2B rows (CriticStep's), every row an ordinary one.
+    """
+
+    @staticmethod
+    def supports(critic):
+        return (CriticStep.supports(critic) and not hasattr(critic, "fc1") and getattr(critic, "audio_d", None) is None
+                and not getattr(critic, "_head_tanh", False) and int(getattr(critic, "_head_act", ACT_NONE)) == ACT_NONE)
+
+    def __init__(self, critic):
+        assert GanCriticStep.supports(critic)
+        super().__init__(critic, 0.0)
+
+    @torch.no_grad()
+    def run(self, real, fake_rows, on_grads=None):
+        """real: (B, T, C) poses [any view of B*T*C], fake_rows: (B*T, C) generator rows (no graph). Sets p.grad of every
+        critic parameter (None on entry). -> {"loss_critic", "err_real", "err_fake"} (0-dim device tensors)."""
+        k = K()
+        dev, dt = fake_rows.device, fake_rows.dtype
+        C = self.stick.conv1.weight.shape[1]
+        B = real.size(0)
+        T = real.numel() // (B * C)
+        R = 2 * B
+        X = torch.empty((R, C, T), dtype=dt, device=dev)
+        X[:B].copy_(real.reshape(B, T, C).transpose(1, 2))
+        X[B:].copy_(fake_rows.view(B, T, C).transpose(1, 2))
+
+        def rows(ch):
+            return torch.empty((R, ch, T), dtype=dt, device=dev)
+
+        a, p, q = self._pose_forward(X, slice(0, R), rows)
+        CH = a[0].shape[1]
+        s = k.gemm_ld(0, a[-1].view(R, CH * T), self.fconv.weight.view(1, CH * T), self.fconv.bias, ACT_NONE)  # (2B, 1)
+        losses, de_s = k.bce_logits_fwd(s.view(R), B, 1.0, B, 0.0, with_dx=True)
+        de_s = de_s.view(R, 1)
+        da, dp = self._pose_backward_data(de_s, a, p, q, rows)
+
+        def put(conv, gw, gb, defer=False):
+            conv.weight.grad, conv.bias.grad = gw, gb
+
+        def ready():
+            if on_grads is not None:
+                on_grads()
+
+        self._pose_weight_grads(de_s, a, p, q, da, dp, X, 0, put, ready)
+        return {"loss_critic": losses[0], "err_real": losses[1], "err_fake": losses[2]}

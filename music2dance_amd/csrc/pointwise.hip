@@ -503,6 +503,59 @@ __global__ void __launch_bounds__(256) m2d_wgan_critic_loss_kernel(const float* 
   }
 }
 
+// ---------------------------------------------------------------- binary cross-entropy on logits
+// torch.nn.BCEWithLogitsLoss(reduction='mean') of the phase-2 `gan` framework (phase2/train.py:204-240) over one or two
+// row segments with constant targets: [0, n0) against t0, [n0, n0 + n1) against t1 (the critic's [real | fake] scores).
+// Elements in fp64 with torch's stable form; every comparison lets a NaN logit through (no fmax / fmin, which return
+// the other operand on gfx9), so a NaN score gives a NaN loss and a NaN gradient.
+__device__ __forceinline__ double bce_elem(double x, double t) {
+  const double relu = x > 0.0 ? x : 0.0;
+  const double ax = x < 0.0 ? -x : x;
+  return relu - x * t + log1p(exp(-ax));
+}
+
+__device__ __forceinline__ double bce_sigmoid(double x) {
+  if (x >= 0.0) return 1.0 / (1.0 + exp(-x));
+  const double e = exp(x);  // (x < 0 or NaN: no overflow, NaN stays NaN)
+  return e / (1.0 + e);
+}
+
+// ONE workgroup: each segment's sum is a fixed-order fp64 reduction (bit-stable from run to run). dx (optional) =
+// d(mean_0 + mean_1) / dx = (sigmoid(x) - t) / n_segment.
+__global__ void __launch_bounds__(256) m2d_bce_logits_fwd_kernel(const float* __restrict__ x, int n0, float t0, int n1,
+                                                                 float t1, float* out, float* dx) {
+  __shared__ double sh[256];
+  double s0 = 0.0, s1 = 0.0;
+  const double inv0 = 1.0 / (double)n0, inv1 = n1 > 0 ? 1.0 / (double)n1 : 0.0;
+  for (int i = threadIdx.x; i < n0; i += 256) {
+    const double v = (double)x[i];
+    s0 += bce_elem(v, t0);
+    if (dx) dx[i] = (float)((bce_sigmoid(v) - (double)t0) * inv0);
+  }
+  for (int i = threadIdx.x; i < n1; i += 256) {
+    const double v = (double)x[n0 + i];
+    s1 += bce_elem(v, t1);
+    if (dx) dx[n0 + i] = (float)((bce_sigmoid(v) - (double)t1) * inv1);
+  }
+  s0 = block_sum_256(s0, sh);
+  s1 = block_sum_256(s1, sh);
+  if (threadIdx.x == 0) {
+    const double m0 = s0 * inv0, m1 = n1 > 0 ? s1 * inv1 : 0.0;
+    out[0] = (float)(m0 + m1);
+    out[1] = (float)m0;
+    out[2] = (float)m1;
+  }
+}
+
+__global__ void __launch_bounds__(256) m2d_bce_logits_bwd_kernel(const float* __restrict__ x, int n0, float t0, int n1,
+                                                                 float t1, const float* __restrict__ gout, float* dx) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n0 + n1) return;
+  const bool first = i < n0;
+  const double inv = 1.0 / (double)(first ? n0 : n1);
+  dx[i] = (float)((double)gout[0] * (bce_sigmoid((double)x[i]) - (double)(first ? t0 : t1)) * inv);
+}
+
 // ---------------------------------------------------------------- pool / upsample
 // MaxPool1d(2,2): y[r, j] = max(x[r, 2j], x[r, 2j+1]), rows = B*C, Lout = L/2
 __global__ void __launch_bounds__(256) m2d_maxpool2_fwd_kernel(const float* x, float* y, size_t rows, int L,
@@ -1093,6 +1146,30 @@ int m2d_cross_entropy_bwd(const float* logits, const long long* labels, const fl
   hipLaunchKernelGGL(m2d_ce_bwd_kernel, dim3(m2d_ceil_div(B, 4)), dim3(256), 0, stream, logits, labels, gout,
                      dlogits, B, C);
   M2D_CHECK_LAUNCH("m2d_cross_entropy_bwd");
+  return M2D_OK;
+}
+
+int m2d_bce_logits_fwd(const float* x, int n0, float t0, int n1, float t1, float* out, float* dx, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n0 <= 0 || n1 < 0 || (long long)n0 + n1 > 0x7fffffffLL || !x || !out)
+    M2D_FAIL(M2D_ERR_ARG, "m2d_bce_logits_fwd: n0 = %d, n1 = %d (n0 > 0, n1 >= 0)", n0, n1);
+  const double n = (double)n0 + (double)n1;
+  M2dProfScope prof(M2D_FAM_REDUCE, stream, 0.0, (dx ? 8.0 : 4.0) * n, "bce_logits_fwd", n0, n1, 0);
+  hipLaunchKernelGGL(m2d_bce_logits_fwd_kernel, dim3(1), dim3(256), 0, stream, x, n0, t0, n1, t1, out, dx);
+  M2D_CHECK_LAUNCH("m2d_bce_logits_fwd");
+  return M2D_OK;
+}
+
+int m2d_bce_logits_bwd(const float* x, int n0, float t0, int n1, float t1, const float* gout, float* dx,
+                       void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n0 <= 0 || n1 < 0 || (long long)n0 + n1 > 0x7fffffffLL || !x || !gout || !dx)
+    M2D_FAIL(M2D_ERR_ARG, "m2d_bce_logits_bwd: n0 = %d, n1 = %d (n0 > 0, n1 >= 0)", n0, n1);
+  const int n = n0 + n1;
+  M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 8.0 * (double)n, "bce_logits_bwd", n0, n1, 0);
+  hipLaunchKernelGGL(m2d_bce_logits_bwd_kernel, dim3(m2d_ceil_div(n, 256)), dim3(256), 0, stream, x, n0, t0, n1, t1,
+                     gout, dx);
+  M2D_CHECK_LAUNCH("m2d_bce_logits_bwd");
   return M2D_OK;
 }
 

@@ -16,10 +16,10 @@ import torch
 import torch.optim as optim
 
 from . import kernels, ops
-from .critic_step import CriticStep
+from .critic_step import CriticStep, GanCriticStep
 from .dp import GradExchange
 from .layers import DrawTape, copy_stream, draw_tape, host_draw, to_device_async
-from .losses import gradient_penalty, tv_loss
+from .losses import bce_with_logits, gradient_penalty, tv_loss
 
 
 class _Freeze:
@@ -586,6 +586,8 @@ class Phase2Engine(WganGpEngine):
     """Unconditional sequence WGAN-LP (phase2/train.py:135-180), with the reference's
     MultiStepLR schedulers stepped on generator iterations only (:179-180)."""
 
+    draws_alpha = True  # the critic iteration takes interpolation weights (a host draw per iteration)
+
     def __init__(self, gen, critic, cfg, **kw):
         super().__init__(gen, critic, cfg["lr_gen"], cfg["lr_critic"], cfg["n_critic_steps"], **kw)
         self.gamma, self.eta = float(cfg["gamma"]), float(cfg["eta"])
@@ -704,7 +706,8 @@ class Phase2Engine(WganGpEngine):
         pend, self._fake_pending = self._fake_pending, None
         main = torch.cuda.current_stream(dev)
         g["real"].copy_(real.reshape(g["real"].shape))
-        g["alpha"].copy_(to_device_async(torch.rand(B, 1), dev))
+        if self.draws_alpha:
+            g["alpha"].copy_(to_device_async(torch.rand(B, 1), dev))
         if pend is not None:
             main.wait_event(pend[1])
         g["fake_in"].copy_(out_rows)
@@ -789,6 +792,56 @@ class Phase2Engine(WganGpEngine):
         torch.cuda.synchronize(dev)
         self._graphs[key] = g
         return g
+
+
+class Phase2GanEngine(Phase2Engine):
+    """The phase-2 `gan` framework (phase2/train.py:204-240): BCEWithLogitsLoss on the critic's scores, a critic and a
+    generator iteration on EVERY loop body (the reference comments its n_critic gating out) and both schedulers stepped
+    on every one. Labels are float (1.0 real, 0.0 fake): the reference's int64 torch.full labels are refused by
+    BCEWithLogitsLoss on current torch. Draws per body, on the host generator under `host_noise`: the critic
+    iteration's noise, then the generator iteration's - no interpolation weights.
+
+    The pipelined generator forward, the captured graphs (enable_graphs), the deferred optimizer steps, the async-fault
+    handling and the data-parallel exchange are Phase2Engine's; the critic iteration is critic_step.GanCriticStep
+    (M2D_MANUAL_CRITIC=0: critic.score_pair + losses.bce_with_logits through autograd)."""
+
+    draws_alpha = False
+
+    def __init__(self, gen, critic, cfg, **kw):
+        cfg = dict(cfg, n_critic_steps=1)   # (whatever the YAML says)
+        cfg.setdefault("gamma", 0.0)          # (no penalty)
+        super().__init__(gen, critic, cfg, **kw)
+        self.manual_critic = None
+        if os.environ.get("M2D_MANUAL_CRITIC", "1") != "0" and GanCriticStep.supports(critic):
+            self.manual_critic = GanCriticStep(critic)
+
+    def _critic_from_fake(self, real, fake_rows, alpha=None):
+        """err_critic = BCE(critic(real), 1) + BCE(critic(fake), 0) (phase2/train.py:217-219); `alpha` is not used."""
+        B = real.size(0)
+        T = real.numel() // (B * self.output_size)
+        if self.manual_critic is not None:
+            return self.manual_critic.run(real, fake_rows, on_grads=self._poll_exchange())
+        fake = fake_rows.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        s_real, s_fake = self.critic.score_pair(real_c, fake)
+        err_real, err_fake = bce_with_logits(s_real, 1.0), bce_with_logits(s_fake, 0.0)
+        err_critic = err_real + err_fake
+        err_critic.backward()
+        return {"loss_critic": err_critic.detach(), "err_real": err_real.detach(), "err_fake": err_fake.detach()}
+
+    def _generator_body(self, real, noise):
+        """err_gen = BCE(critic(fake), 1) + eta * tv_loss(fake) (phase2/train.py:230-233), the critic frozen: the
+        reference's critic gradients of this step are zeroed before anything reads them."""
+        B = real.size(0)
+        T = real.numel() // (B * self.output_size)
+        self.optim_gen.zero_grad(set_to_none=True)
+        if noise is None:
+            noise = self._noise(B, T, real.device)
+        fake = self.gen(noise, [T] * B).view(B, T, self.output_size).permute(0, 2, 1)
+        with _Freeze(self.critic):
+            err_gen = bce_with_logits(self.critic(fake), 1.0) + self.eta * tv_loss(fake)
+            err_gen.backward()
+        return {"loss_gen": err_gen.detach()}
 
 
 # =========================================================================================== phase 1

@@ -1117,6 +1117,36 @@ class HipKernels:
         _lib.check(rc, "m2d_cross_entropy_bwd")
         return dlogits
 
+    @staticmethod
+    def _chk_bce(x, n0, n1):
+        if not x.is_contiguous() or x.numel() != n0 + n1:
+            raise _lib.M2dError("bce on logits: %d contiguous logits expected for segments of %d + %d"
+                                % (x.numel(), n0, n1))
+
+    def bce_logits_fwd(self, x, n0, t0, n1=0, t1=0.0, with_dx=False):
+        """BCEWithLogitsLoss(mean) of logits[:n0] against t0 plus that of logits[n0:n0 + n1] against t1 ->
+        (out (3,) = (sum of the two means, mean_0, mean_1), dx = d out[0] / d logits (shape of x) or None)"""
+        dev = _chk(x)
+        self._chk_bce(x, n0, n1)
+        out = torch.empty((3,), dtype=torch.float32, device=dev)
+        dx = torch.empty_like(x) if with_dx else None
+        with _on(dev):
+            rc = _lib.lib().m2d_bce_logits_fwd(_ptr(x), int(n0), float(t0), int(n1), float(t1), _ptr(out), _ptr(dx),
+                                               _stream(dev))
+        _lib.check(rc, "m2d_bce_logits_fwd")
+        return out, dx
+
+    def bce_logits_bwd(self, x, n0, t0, n1, t1, gout):
+        """dx = gout[0] * (sigmoid(x) - t) / n_segment; gout a device scalar"""
+        dev = _chk(x, gout)
+        self._chk_bce(x, n0, n1)
+        dx = torch.empty_like(x)
+        with _on(dev):
+            rc = _lib.lib().m2d_bce_logits_bwd(_ptr(x), int(n0), float(t0), int(n1), float(t1), _ptr(gout), _ptr(dx),
+                                               _stream(dev))
+        _lib.check(rc, "m2d_bce_logits_bwd")
+        return dx
+
     def tv_mean_fwd(self, x, B, C, T, sb, sc, st):
         """x: storage holding a (B, C, T) view with element strides (sb, sc, st)."""
         dev = _chk(x)

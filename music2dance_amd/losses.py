@@ -68,3 +68,10 @@ def cross_entropy(logits, target):
     """torch.nn.CrossEntropyLoss(reduction='mean') of the dance classifier (dance_classification/main.py:126) on the
     HIP kernels: logits (B, C), int64 class indices (B,)."""
     return ops.cross_entropy(logits, target)
+
+
+def bce_with_logits(logits, target):
+    """torch.nn.BCEWithLogitsLoss(reduction='mean') of the phase-2 `gan` framework (phase2/train.py:205) on the HIP
+    kernels: the drop-in for the reference's criterion(scores, label), with the label a constant - 1.0 for real rows,
+    0.0 for fake ones - given as one number."""
+    return ops.bce_with_logits(logits, target)

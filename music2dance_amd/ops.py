@@ -824,6 +824,32 @@ def cross_entropy(logits, target):
     return _CrossEntropy.apply(logits, target)
 
 
+class _BCEWithLogits(Function):
+    @staticmethod
+    def forward(ctx, logits, target):
+        ctx.set_materialize_grads(False)
+        x = _c(logits).view(-1)
+        out, _ = K().bce_logits_fwd(x, x.numel(), target)
+        ctx.save_for_backward(x)
+        ctx.target, ctx.shape = target, logits.shape
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None
+        x, = ctx.saved_tensors
+        return K().bce_logits_bwd(x, x.numel(), ctx.target, 0, 0.0, _c(gout)).view(ctx.shape), None
+
+
+def bce_with_logits(logits, target):
+    """torch.nn.BCEWithLogitsLoss(reduction='mean')(logits, full_like(logits, target)): a CONSTANT float target."""
+    if torch.is_tensor(target) or not isinstance(target, (int, float)):
+        raise TypeError("bce_with_logits: the target is one Python number (got %s)" % type(target).__name__)
+    return _BCEWithLogits.apply(logits, float(target))
+
+
 def cross_entropy_pred(logits, target):
     """(loss, argmax of each row) from one launch pair, no graph: the evaluation form."""
     target = target.reshape(-1).to(torch.int64).contiguous()

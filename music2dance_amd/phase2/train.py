@@ -1,17 +1,20 @@
-"""Phase 2: unconditional sequence WGAN-GP/LP on MI355X.
+"""Phase 2: unconditional sequence GAN on MI355X, WGAN-LP (`-f wgangp`) or vanilla (`-f gan`).
 
     python -m music2dance_amd.phase2.train -c music2dance_amd/phase2/configs/default.yaml -d 0 -n run -f wgangp --synthetic
+    python -m music2dance_amd.phase2.train -c music2dance_amd/phase2/configs/default.yaml -d 0 -n run -f gan --synthetic
 
-Flags -c/-d/-n/-f and YAML keys as in the reference's phase2/train.py. Only the `wgangp`
-framework is part of this engine; `gan` (BCE) is outside the WGAN-GP path and, like any
-unknown value, is rejected with the reference's error.
+Flags -c/-d/-n/-f and YAML keys as in the reference's phase2/train.py. `wgangp` runs engine.Phase2Engine
+(phase2/train.py:130-195) and logs loss_critic / loss_gen / gp / w_dist; `gan` runs engine.Phase2GanEngine
+(phase2/train.py:204-268): BCEWithLogitsLoss with float labels (the reference's int64 labels are refused by current
+torch), a generator step and both scheduler steps on every iteration, scalars logged as loss_D / loss_G. Both keep this
+port's checkpoint schedule (gpgen_ / gpcritic_ every 5000 epochs). Any other value raises the reference's error.
 """
 import argparse
 
 import torch
 
 from .. import dp, runner
-from ..engine import Phase2Engine
+from ..engine import Phase2Engine, Phase2GanEngine
 from .archis.default import SequenceDiscriminator, SequenceGenerator
 
 
@@ -37,7 +40,7 @@ def main(argv=None):
                     help="fetch and collate batches on the host (torch DataLoader) instead of gathering them from the "
                          "HBM-resident dataset; same batches either way")
     opts = ap.parse_args(argv)
-    if opts.framework != "wgangp":
+    if opts.framework not in ("wgangp", "gan"):
         raise ValueError("Please state existing framework")
 
     rank, world, local = dp.init_from_env()
@@ -71,7 +74,8 @@ def main(argv=None):
     if next(critic.parameters()).is_cuda:
         from .. import kernels
         kernels.set_plan_model(5)   # no second critic branch to overlap with: the launch-by-launch cost model
-    engine = Phase2Engine(gen, critic, cfg, sync_bn=opts.sync_bn)
+    gan = opts.framework == "gan"
+    engine = (Phase2GanEngine if gan else Phase2Engine)(gen, critic, cfg, sync_bn=opts.sync_bn)
     torch.manual_seed(rank)  # identical weights (seed 0 above), rank-distinct noise / alpha draws
     engine.host_noise = False  # phase2/train.py:139-140 draws the noise on the device
     if device.type == "cuda" and (opts.graphs or (world == 1 and not opts.no_graphs)):
@@ -98,7 +102,9 @@ def main(argv=None):
         for real in source:
             out = engine.train_step(real)
             it = engine.total_iterations
-            if "loss_gen" in out:
+            if gan:
+                log.scalars({"loss_D": out["loss_critic"], "loss_G": out["loss_gen"]}, it)
+            elif "loss_gen" in out:
                 log.scalars({"loss_critic": -out["loss_critic"], "loss_gen": out["loss_gen"], "gp": out["gp"],
                              "w_dist": -out["w_dist"]}, it)
             if opts.iterations is not None and it >= opts.iterations:
