@@ -391,6 +391,28 @@ int m2d_upsample2_fwd_to(const float* x, float* y, size_t B, int C, int L, long 
 int m2d_maxpool2_fwd_from(const float* x, float* y, size_t B, int C, int L, long long x_batch_stride, void* stream);
 int m2d_upsample2_bwd(const float* dy, float* dx, size_t rows, int L, void* stream);
 
+/* ---- label conditioning and dropout of the conditional phase-2 networks (phase2/archis/conditional.py) ---------- */
+/* out = [x | E[labels[b]]] for every (b, t). layout 0 (batch-first): x (B, T, C), out (B, T, C + D); layout 1
+   (channels-first): x (B, C, T), out (B, C + D, T). E (L, D); labels int64 (B,). A label outside [0, L) makes the D
+   label features of its row NaN (nothing is read out of bounds). */
+int m2d_label_concat(const float* x, const float* E, const long long* labels, float* out, int B, int T, int C, int L,
+                     int D, int layout, void* stream);
+/* m2d_pose_pack3 with label channels: out (3B, C + D, T) = [interpolated | real | fake] channels-first; the interpolated
+   and real rows carry E[real_lbl[b]], the fake rows E[fake_lbl[b]], constant over time */
+int m2d_pose_pack3_label(const float* real, const float* fake, const float* alpha, const float* E,
+                         const long long* real_lbl, const long long* fake_lbl, float* out, int B, int T, int C, int L,
+                         int D, void* stream);
+/* dE[l, d] = sum over rows r in [r0, r1) with labels[r - r0] == l of sum_t dx[r, c0 + d, t] (layout 0: dx (R, T, Ctot),
+   layout 1: dx (R, Ctot, T)); dE (L, D) is overwritten. One workgroup per (l, d), fixed-order fp64 sum, no atomics:
+   bit-stable. Any label of the range outside [0, L): every dE entry is NaN. */
+int m2d_label_embed_bwd(const float* dx, const long long* labels, float* dE, int r0, int r1, int T, int Ctot, int c0,
+                        int L, int D, int layout, void* stream);
+/* y = x * keep * scale over n elements. gen = 0: keep = mask[i] != 0 (bytes). gen = 1: keep = (u >> 8) * 2^-24 < p_keep
+   with u word i % 4 of Philox4x32-10(counter = (i / 4, offset), key = seed); mask (optional) receives the keep bytes.
+   x = NULL: the mask only (gen = 1). */
+int m2d_dropout(const float* x, float* y, unsigned char* mask, long long n, float p_keep, float scale,
+                unsigned long long seed, unsigned long long offset, int gen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

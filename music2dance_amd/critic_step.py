@@ -157,9 +157,10 @@ class CriticStep:
             a.append(ak)
         return a, p, q
 
-    def _pose_backward_data(self, de_s, a, p, q, rows):
+    def _pose_backward_data(self, de_s, a, p, q, rows, head_keep=None):
         """backward-data chain of the pose branch for the (R, Cc) cotangents de_s at the full-length conv's output ->
-        (da, dp): the gradients at every block input (da[0]: after conv1's ReLU) and at every block's first conv"""
+        (da, dp): the gradients at every block input (da[0]: after conv1's ReLU) and at every block's first conv.
+        head_keep: the uint8 keep mask of a dropout in front of the full-length conv (CondCriticStep)"""
         k = K()
         st = self.stick
         nb = len(st.blocks)
@@ -168,6 +169,8 @@ class CriticStep:
         da = [rows(CH) for _ in range(nb + 1)]
         dp = [rows(CH) for _ in range(nb)]
         k.gemm(1, de_s, fw2d, out=da[nb].view(R, CH * T))
+        if head_keep is not None:
+            da[nb] = k.dropout(da[nb], head_keep, p_keep=self.keep_p, scale=1.0 / self.keep_p)
         for i in range(nb - 1, -1, -1):
             blk = st.blocks[i]
             wa, _, _, pa = _conv_params(blk.conv1)
@@ -178,17 +181,18 @@ class CriticStep:
             da[0] = da[0] * (a[0] > 0)
         return da, dp
 
-    def _pose_weight_grads(self, c, a, p, q, da, dp, X, b0, put, ready):
+    def _pose_weight_grads(self, c, a, p, q, da, dp, X, b0, put, ready, head_in=None):
         """weight gradients of the pose branch, one launch per layer over all R rows, in reverse parameter order: c (R, Cc)
         the cotangents at the full-length conv's output. Bias gradients sum rows [b0, R) only (rows in front pair
-        second-order operands). put(conv, dW, db, defer) binds them; ready (or None) after each layer's."""
+        second-order operands). put(conv, dW, db, defer) binds them; ready (or None) after each layer's.
+        head_in: the full-length conv's input when it is not a[-1] (the dropped rows of CondCriticStep)"""
         k = K()
         st = self.stick
         nb = len(st.blocks)
         R, CH, T = a[0].shape
         w1, _, _, pad1 = _conv_params(st.conv1)
         defer = ready is None
-        put(self.fconv, k.gemm(2, c, a[nb].view(R, CH * T)).view(self.fconv.weight.shape),
+        put(self.fconv, k.gemm(2, c, (a[nb] if head_in is None else head_in).view(R, CH * T)).view(self.fconv.weight.shape),
             k.channel_sums(c[b0:].contiguous()), defer=defer)
         if ready is not None:
             ready()
@@ -525,3 +529,106 @@ class GanCriticStep(CriticStep):
 
         self._pose_weight_grads(de_s, a, p, q, da, dp, X, 0, put, ready)
         return {"loss_critic": losses[0], "err_real": losses[1], "err_fake": losses[2]}
+
+
+class CondCriticStep(CriticStep):
+    """The critic iteration of the conditional phase-2 WGAN-LP (train_conditional.py:109-140 with the archis of
+    phase2/archis/conditional.py) as one hand-scheduled pass:
+    err_critic = mean(D(fake, fake_lbl)) - mean(D(real, real_lbl)) + gamma * LP, the interpolates scored with the REAL
+    labels, LP = mean max(0, ||d D / d poses|| - 1)^2.
+
+      forward        pose branch once over 3B rows [interpolated | real | fake], (69 + 4) channels each:
+                     m2d_pose_pack3_label writes the poses and the label channels; the dropout mask (3B, CH, T) of
+                     the three critic calls multiplies the full-length conv's input.
+      backward-data  CriticStep's chain, the mask applied to the full-length conv's input gradient; conv1's
+                     backward-data runs over all 3B rows in one launch: rows [0, B) give the penalty's input gradient,
+                     whose norm covers the 69 POSE channels only, rows [B, 3B) the label channels' gradient.
+      embedding      dE from the real (cotangent -1/B) and fake (+1/B) rows only (m2d_label_embed_bwd): E reaches the
+                     penalty through ReLU masks alone, so its penalty derivative is exactly zero.
+      tangent        the penalty's tangent over the interpolated rows with ZERO label channels (conv1's second-order
+                     weight-gradient term has no label-channel part), the mask applied at the full-length conv.
+      weight grads   CriticStep's pairing; the full-length conv pairs with the masked rows.
+    """
+
+    @staticmethod
+    def supports(critic):
+        return (hasattr(critic, "embed_label") and hasattr(critic, "dropout") and CriticStep.supports(critic)
+                and not hasattr(critic, "fc1") and getattr(critic, "audio_d", None) is None
+                and not getattr(critic, "_head_tanh", False) and int(getattr(critic, "_head_act", ACT_NONE)) == ACT_NONE)
+
+    def __init__(self, critic, gamma, lp=True):
+        assert CondCriticStep.supports(critic)
+        super().__init__(critic, gamma, lp)
+        self.keep_p = 1.0 - float(critic.dropout.p)
+
+    @torch.no_grad()
+    def run(self, real, fake_rows, real_lbl, fake_lbl, alpha, keep=None, on_grads=None):
+        """real: (B, T, 69) poses [any view of B*T*69], fake_rows: (B*T, 69) generator rows (no graph), real_lbl /
+        fake_lbl: (B,) int64, alpha: (B, 1) or (B,) interpolation weights, keep: the (3B, CH, T) uint8 keep mask of the
+        [interpolated | real | fake] critic calls, or None: Philox bits made on the device in the forward's dropout
+        launch. Sets p.grad of every critic parameter (None on entry). -> {"loss_critic", "gp", "w_dist"}."""
+        k = K()
+        st = self.stick
+        dev, dt = fake_rows.device, fake_rows.dtype
+        E = self.critic.embed_label.weight
+        L, D = E.shape
+        w1, _, _, pad1 = _conv_params(st.conv1)
+        Cin = w1.shape[1]
+        C = Cin - D
+        B = real.size(0)
+        T = real.numel() // (B * C)
+        R = 3 * B
+        tg = slice(0, B)
+        c1, _, gamma_t = self._constants(B, dev, dt)
+        nb = len(st.blocks)
+        CH = w1.shape[0]
+        fw2d = self.fconv.weight.view(self.fconv.weight.shape[0], CH * T)
+        sp = dict(p_keep=self.keep_p, scale=1.0 / self.keep_p)
+
+        def rows(ch):
+            return torch.empty((R, ch, T), dtype=dt, device=dev)
+
+        # ---------------------------------------------------------------- forward
+        X = k.pose_pack3_label(real.reshape(B, T, C), fake_rows, alpha.reshape(B), E, real_lbl, fake_lbl)
+        a, p, q = self._pose_forward(X, slice(0, R), rows)
+        if keep is None:
+            from . import ops
+            seed, off = ops.philox_next()
+            keep = torch.empty((R, CH, T), dtype=torch.uint8, device=dev)
+            h = k.dropout(a[nb], keep, seed=seed, offset=off, **sp)
+        else:
+            h = k.dropout(a[nb], keep, **sp)
+        s = k.gemm_ld(0, h.view(R, CH * T), fw2d, self.fconv.bias, ACT_NONE)   # (3B, 1)
+
+        # ---------------------------------------------------------------- backward-data, penalty, embedding
+        da, dp = self._pose_backward_data(c1, a, p, q, rows, head_keep=keep)
+        dX = k.conv1d_bwd_data(da[0], w1, T, 1, pad1)                          # (3B, 69 + 4, T)
+        v_pose = dX[tg, :C].contiguous()
+        pen, norms = k.gp_penalty_fwd(v_pose.view(B, -1), self.lp)
+        lbl2 = torch.cat((real_lbl, fake_lbl))
+        dE = k.label_embed_bwd(dX, lbl2, B, R, C, L, D, 1)
+        losses = k.wgan_critic_loss(s.view(-1), B, pen, None, self.gamma)
+
+        # ---------------------------------------------------------------- tangent (label channels zero)
+        X[tg, C:].zero_()
+        X[tg, :C] = k.gp_penalty_bwd(v_pose.view(B, -1), norms, gamma_t, self.lp).view(B, C, T)
+        k.conv1d_fwd(X[tg], w1, None, 1, pad1, ACT_NONE, out_mask=a[0][tg], out=a[0][tg])
+        for i, blk in enumerate(st.blocks):
+            wa, _, _, pa = _conv_params(blk.conv1)
+            wb, _, _, pb = _conv_params(blk.conv2)
+            k.conv1d_fwd(a[i][tg], wa, None, 1, pa, ACT_NONE, out_mask=p[i][tg], out=p[i][tg])
+            k.conv1d_fwd(p[i][tg], wb, None, 1, pb, ACT_NONE, residual=a[i][tg], out_mask=q[i][tg], out=a[i + 1][tg])
+        k.dropout(a[nb][tg], keep[tg], out=h[tg], **sp)
+
+        # ---------------------------------------------------------------- weight gradients
+        def put(conv, gw, gb, defer=False):
+            conv.weight.grad, conv.bias.grad = gw, gb
+
+        def ready():
+            if on_grads is not None:
+                on_grads()
+
+        self._pose_weight_grads(c1, a, p, q, da, dp, X, B, put, ready, head_in=h)
+        E.grad = dE
+        ready()
+        return {"loss_critic": losses[0], "gp": losses[1], "w_dist": losses[2]}

@@ -16,9 +16,9 @@ import torch
 import torch.optim as optim
 
 from . import kernels, ops
-from .critic_step import CriticStep, GanCriticStep
+from .critic_step import CondCriticStep, CriticStep, GanCriticStep
 from .dp import GradExchange
-from .layers import DrawTape, copy_stream, draw_tape, host_draw, to_device_async
+from .layers import DrawTape, Dropout, copy_stream, draw_tape, host_draw, to_device_async
 from .losses import bce_with_logits, gradient_penalty, tv_loss
 
 
@@ -840,6 +840,145 @@ class Phase2GanEngine(Phase2Engine):
         fake = self.gen(noise, [T] * B).view(B, T, self.output_size).permute(0, 2, 1)
         with _Freeze(self.critic):
             err_gen = bce_with_logits(self.critic(fake), 1.0) + self.eta * tv_loss(fake)
+            err_gen.backward()
+        return {"loss_gen": err_gen.detach()}
+
+
+class Phase2CondEngine(Phase2Engine):
+    """The label-conditioned phase-2 WGAN-LP: the `wgangp` loop of train_conditional.py:109-185, changed only where the
+    archis of phase2/archis/conditional.py force it. err_critic = mean(D(fake, fake_lbl)) -
+    mean(D(real, real_lbl)) + gamma * LP, the interpolates scored with the real labels; err_gen = mean(D(real, real_lbl))
+    - mean(D(fake, fake_lbl)) + eta * tv_loss(fake) every n_critic_steps-th body; plain Adam, no schedulers. Every fake
+    batch gets its own labels, uniform over {0..3}.
+
+    Draws per body, in this order (host generator under `host_noise`, parity mode; on the device otherwise, dropout
+    masks from Philox4x32-10): critic iteration - fake labels, noise, the decoder's dropout mask, alpha, the critic's
+    masks for the interpolated, real and fake rows; generator iteration - labels, noise, the decoder's mask, the
+    critic's masks for real, then fake (the real scoring only feeds the logged value; its mask is drawn all the same).
+
+    The pipelined generator forward, the deferred optimizer steps, the async-fault checks and the data-parallel exchange
+    are Phase2Engine's (the embeddings ride in the existing buckets). The critic iteration is critic_step.CondCriticStep
+    (M2D_MANUAL_CRITIC=0: critic(x, labels) and losses.gradient_penalty(..., labels=) through autograd). Captured
+    graphs are not supported."""
+
+    n_classes = 4
+
+    def __init__(self, gen, critic, cfg, **kw):
+        super().__init__(gen, critic, cfg, **kw)
+        self.manual_critic = None
+        if os.environ.get("M2D_MANUAL_CRITIC", "1") != "0" and CondCriticStep.supports(critic):
+            self.manual_critic = CondCriticStep(critic, self.gamma, lp=True)
+
+    @property
+    def host_noise(self):
+        return self._host
+
+    @host_noise.setter
+    def host_noise(self, on):
+        """True: every draw on the host generator, as the reference's CPU path makes it; False: on the device"""
+        self._host = bool(on)
+        for net in (self.gen, self.critic):
+            for m in net.modules():
+                if isinstance(m, Dropout):
+                    m.host_rng = self._host
+
+    host_rng = host_noise
+
+    def _labels(self, B, device):
+        if self.host_noise:
+            return to_device_async(torch.randint(0, self.n_classes, (B,)), device)
+        return torch.randint(0, self.n_classes, (B,), device=device)
+
+    def _critic_keep(self, B, T, device):
+        """the uint8 keep mask of the critic's [interpolated | real | fake] calls (host mode), or None: made on the
+        device by CondCriticStep"""
+        if not self.host_noise:
+            return None
+        ch = self.critic.lastconv.weight.shape[1]
+        p = 1.0 - float(self.critic.dropout.p)
+        host = torch.cat([torch.empty(B, ch, T).bernoulli_(p) for _ in range(3)]).to(torch.uint8)
+        return to_device_async(host, device)
+
+    @staticmethod
+    def _real_labels(real_labels, device):
+        return real_labels.reshape(-1).to(device=device, dtype=torch.int64, non_blocking=True).contiguous()
+
+    def enable_graphs(self, on=True):
+        if on:
+            raise NotImplementedError("Phase2CondEngine: captured-graph mode is not supported for the conditional loop")
+        self._use_graphs = False
+        self._graphs = {}
+        return self
+
+    def train_step(self, real, real_labels, inputs_ready=None):
+        return WganGpEngine.train_step(self, real, self._real_labels(real_labels, real.device), inputs_ready=inputs_ready)
+
+    def critic_iteration(self, real, real_labels):
+        out = self._critic_body(real, self._real_labels(real_labels, real.device))
+        self._begin_critic_step()
+        return out
+
+    def _critic_body(self, real, real_labels, noise=None, alpha=None):
+        B = real.size(0)
+        T = real.numel() // (B * self.output_size)
+        dev = real.device
+        self._always_ready(dev)
+        drawn = []
+
+        def forward():
+            # (on the generator's stream when it runs ahead: the labels are then produced there too)
+            lbl = self._labels(B, dev)
+            drawn.append(lbl)
+            return self.gen(self._noise(B, T, dev) if noise is None else noise, lbl)
+
+        fake_rows = self._generator_forward_nograd(forward, (), dev)
+        fake_lbl = drawn[0]
+        self._finish_critic_step()
+        self.optim_critic.zero_grad(set_to_none=True)
+        self._join_generator_forward(fake_rows)
+        if dev.type == "cuda":
+            fake_lbl.record_stream(torch.cuda.current_stream(dev))
+        if alpha is None:
+            alpha = to_device_async(torch.rand(B, 1), dev) if self.host_noise else torch.rand(B, 1, device=dev)
+        return self._cond_critic(real, real_labels, fake_rows, fake_lbl, alpha)
+
+    def _cond_critic(self, real, real_labels, fake_rows, fake_lbl, alpha):
+        B = real.size(0)
+        T = real.numel() // (B * self.output_size)
+        if self.manual_critic is not None:
+            return self.manual_critic.run(real, fake_rows, real_labels, fake_lbl, alpha,
+                                          keep=self._critic_keep(B, T, real.device), on_grads=self._poll_exchange())
+        fake = fake_rows.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        gp = gradient_penalty(self.critic, B, real_c, fake, is_seq=True, lp=True, device=real.device, alpha=alpha,
+                              labels=real_labels)
+        err_real = self.critic(real_c, real_labels).mean()
+        err_fake = self.critic(fake, fake_lbl).mean()
+        err_critic = err_fake - err_real + self.gamma * gp
+        err_critic.backward()
+        return {"loss_critic": err_critic.detach(), "gp": gp.detach(), "w_dist": (err_fake - err_real).detach()}
+
+    def generator_iteration(self, real, real_labels):
+        self._finish_critic_step()
+        out = self._generator_body(real, self._real_labels(real_labels, real.device))
+        self._gen_step()   # (train_conditional.py:80-81: plain Adam, no schedulers)
+        return out
+
+    def _generator_body(self, real, real_labels, noise=None):
+        B = real.size(0)
+        T = real.numel() // (B * self.output_size)
+        dev = real.device
+        self.optim_gen.zero_grad(set_to_none=True)
+        lbl = self._labels(B, dev)
+        if noise is None:
+            noise = self._noise(B, T, dev)
+        fake = self.gen(noise, lbl).view(B, T, self.output_size).permute(0, 2, 1)
+        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        with _Freeze(self.critic):
+            with torch.no_grad():
+                err_real = self.critic(real_c, real_labels).mean()
+            err_fake = self.critic(fake, lbl).mean()
+            err_gen = err_real - err_fake + self.eta * tv_loss(fake)
             err_gen.backward()
         return {"loss_gen": err_gen.detach()}
 

@@ -1147,6 +1147,85 @@ class HipKernels:
         _lib.check(rc, "m2d_bce_logits_bwd")
         return dx
 
+    # ---------------------------------------------------------------- label conditioning and dropout (cond.hip)
+    @staticmethod
+    def _chk_class_indices(labels, n, dev):
+        if labels.dtype != torch.int64 or not labels.is_contiguous() or labels.numel() != n or labels.device != dev:
+            raise _lib.M2dError("labels: %d contiguous int64 values on %s expected" % (n, dev))
+
+    def label_concat(self, x, E, labels, layout, out=None):
+        """[x | E[labels[b]]]: layout 0 x (B, T, C) -> (B, T, C + D); layout 1 x (B, C, T) -> (B, C + D, T)"""
+        dev = _chk(x, E, out)
+        B = x.shape[0]
+        self._chk_class_indices(labels, B, dev)
+        L, D = E.shape
+        if layout == 0:
+            T, C = x.shape[1], x.shape[2]
+            shape = (B, T, C + D)
+        else:
+            C, T = x.shape[1], x.shape[2]
+            shape = (B, C + D, T)
+        o = torch.empty(shape, dtype=torch.float32, device=dev) if out is None else out
+        assert tuple(o.shape) == shape
+        with _on(dev):
+            rc = _lib.lib().m2d_label_concat(_ptr(x), _ptr(E), _ptr(labels), _ptr(o), B, T, C, L, D, int(layout),
+                                             _stream(dev))
+        _lib.check(rc, "m2d_label_concat")
+        return o
+
+    def pose_pack3_label(self, real, fake_rows, alpha, E, real_lbl, fake_lbl, out=None):
+        """real (B, T, C), fake_rows (B*T, C), alpha (B,), E (L, D) -> (3B, C + D, T) = [interpolated | real | fake]
+        channels-first with the label channels (real labels on the first two blocks, fake labels on the last)."""
+        dev = _chk(real, fake_rows, alpha, E, out)
+        B, T, C = real.shape
+        L, D = E.shape
+        assert fake_rows.numel() == real.numel() and alpha.numel() == B
+        self._chk_class_indices(real_lbl, B, dev)
+        self._chk_class_indices(fake_lbl, B, dev)
+        o = torch.empty((3 * B, C + D, T), dtype=torch.float32, device=dev) if out is None else out
+        assert tuple(o.shape) == (3 * B, C + D, T)
+        with _on(dev):
+            rc = _lib.lib().m2d_pose_pack3_label(_ptr(real), _ptr(fake_rows), _ptr(alpha), _ptr(E), _ptr(real_lbl),
+                                                 _ptr(fake_lbl), _ptr(o), B, T, C, L, D, _stream(dev))
+        _lib.check(rc, "m2d_pose_pack3_label")
+        return o
+
+    def label_embed_bwd(self, dx, labels, r0, r1, c0, L, D, layout, out=None):
+        """dE (L, D) = per class, the sum over rows [r0, r1) carrying it (labels: one per row of the range) of
+        dx[row, c0:c0 + D, :] summed over time; layout 0: dx (R, T, Ctot), layout 1: dx (R, Ctot, T)"""
+        dev = _chk(dx, out)
+        self._chk_class_indices(labels, r1 - r0, dev)
+        assert 0 <= r0 < r1 <= dx.shape[0]
+        T, Ctot = (dx.shape[1], dx.shape[2]) if layout == 0 else (dx.shape[2], dx.shape[1])
+        o = torch.empty((L, D), dtype=torch.float32, device=dev) if out is None else out
+        with _on(dev):
+            rc = _lib.lib().m2d_label_embed_bwd(_ptr(dx), _ptr(labels), _ptr(o), int(r0), int(r1), T, Ctot, int(c0),
+                                                int(L), int(D), int(layout), _stream(dev))
+        _lib.check(rc, "m2d_label_embed_bwd")
+        return o
+
+    def dropout(self, x, mask, p_keep=0.5, scale=2.0, seed=None, offset=0, out=None):
+        """y = x * keep * scale. seed None: keep from the uint8 `mask` (the caller's); else Philox4x32-10 bits of
+        (seed, offset, index), written into `mask` when given. x None: the mask only. -> y (or mask)."""
+        gen = seed is not None
+        dev = _chk(x, out)
+        if mask is not None:
+            if mask.dtype != torch.uint8 or not mask.is_contiguous():
+                raise _lib.M2dError("dropout: a contiguous uint8 mask expected")
+            dev = dev or mask.device
+            if x is not None and mask.numel() != x.numel():
+                raise _lib.M2dError("dropout: mask and input differ in size")
+        if not gen and mask is None:
+            raise _lib.M2dError("dropout: a mask or a seed is needed")
+        n = x.numel() if x is not None else mask.numel()
+        y = (torch.empty_like(x) if out is None else out) if x is not None else None
+        with _on(dev):
+            rc = _lib.lib().m2d_dropout(_ptr(x), _ptr(y), _ptr(mask), n, float(p_keep), float(scale),
+                                        int(seed or 0) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, int(gen),
+                                        _stream(dev))
+        _lib.check(rc, "m2d_dropout")
+        return y if x is not None else mask
+
     def tv_mean_fwd(self, x, B, C, T, sb, sc, st):
         """x: storage holding a (B, C, T) view with element strides (sb, sc, st)."""
         dev = _chk(x)

@@ -293,10 +293,17 @@ class Dropout(nn.Dropout):
     seeded runs match the reference's CPU results. `host_rng=False` draws on the device."""
 
     host_rng = True
+    # hip = True (the conditional phase-2 networks): the keep mask and the apply run on m2d_dropout (ops.dropout) - the
+    # host draw as above, or Philox4x32-10 bits made on the device - and the uint8 mask of the last call stays in
+    # `last_mask`
+    hip = False
 
     def forward(self, x):
         if not self.training or self.p == 0.0:
             return x
+        if self.hip:
+            y, self.last_mask = ops.dropout(x, self.p, host=self.host_rng)
+            return y
         if self.host_rng:
             keep = host_draw("bernoulli", x.shape, x.device, 1.0 - self.p, x.dtype)
         else:

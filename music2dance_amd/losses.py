@@ -14,7 +14,7 @@ from .layers import host_draw, to_device_async  # noqa: F401
 
 
 def gradient_penalty(critic, bsize, real, fake, audio=None, is_seq=False, is_cond=False, lp=False, device=None,
-                     alpha=None):
+                     alpha=None, labels=None):
     """Gradient penalty for the stick (phase 1) and sequence (phase 2/3) WGAN frameworks.
 
     lp=False: WGAN-GP  mean_b (sqrt(sum g_b^2 + 1e-12) - 1)^2
@@ -24,7 +24,9 @@ def gradient_penalty(critic, bsize, real, fake, audio=None, is_seq=False, is_con
     default HOST generator (losses.py:15) and `audio.requires_grad_(True)` is applied to
     the caller's tensor (losses.py:26-27). `alpha` (extension, (bsize, 1) on the device): use
     these interpolation weights instead of drawing them (captured-graph replays feed the draw
-    through a static buffer)."""
+    through a static buffer). `labels` (extension, (bsize,) class indices): score the interpolates as
+    critic(interpolates, labels) - the label-conditioned critic of phase2/archis/conditional.py, given the REAL rows'
+    labels."""
     real2d = real.reshape(real.size(0), -1)
     fake2d = fake.reshape(fake.size(0), -1)
     if alpha is None:
@@ -39,7 +41,7 @@ def gradient_penalty(critic, bsize, real, fake, audio=None, is_seq=False, is_con
             score = score[0]
         inputs = (interpol, audio)
     else:
-        score = critic(interpol)
+        score = critic(interpol) if labels is None else critic(interpol, labels)
         if is_cond:
             score = score[0]
         inputs = (interpol,)

@@ -926,3 +926,88 @@ def upsample2_linear(x, out=None):
         assert not (torch.is_grad_enabled() and x.requires_grad)
         return K().upsample2_fwd(_c(x), out=out)
     return _Upsample2.apply(x)
+
+
+# --------------------------------------------------------------------------------------- label conditioning, dropout
+# (phase2/archis/conditional.py). [x | E[label]] and its table gradient on m2d_label_concat / m2d_label_embed_bwd; the
+# input's gradient is the leading C channels of the output's (a differentiable slice: the penalty's double backward
+# passes through it). Dropout y = x * keep * 2 on m2d_dropout with a uint8 keep mask that every later pass reuses.
+class _LabelConcat(Function):
+    @staticmethod
+    def forward(ctx, x, E, labels, layout):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(labels)
+        ctx.layout, ctx.C, ctx.LD = layout, x.shape[2] if layout == 0 else x.shape[1], tuple(E.shape)
+        return K().label_concat(_c(x.detach()), _c(E.detach()), labels, layout)
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None, None, None
+        labels, = ctx.saved_tensors
+        C, (L, D) = ctx.C, ctx.LD
+        gx = gE = None
+        if ctx.needs_input_grad[0]:
+            gx = gout[:, :, :C] if ctx.layout == 0 else gout[:, :C]
+        if ctx.needs_input_grad[1] and not _state["inputs_only"]:
+            gE = K().label_embed_bwd(_c(gout.detach()), labels, 0, gout.shape[0], C, L, D, ctx.layout)
+        return gx, gE, None, None
+
+
+def label_concat(x, E, labels, layout):
+    """[x | E[labels]] along features: layout 0 x (B, T, C) -> (B, T, C + D) (the generator's GRU input), layout 1 x
+    (B, C, T) -> (B, C + D, T) (the critic's conv1 input). labels (B,) integer class indices."""
+    labels = labels.reshape(-1).to(device=x.device, dtype=torch.int64).contiguous()
+    return _LabelConcat.apply(x, E, labels, int(layout))
+
+
+class _Dropout(Function):
+    @staticmethod
+    def forward(ctx, x, mask, seed, offset, p):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mask)
+        ctx.p = p
+        return K().dropout(_c(x.detach()), mask, p_keep=1.0 - p, scale=1.0 / (1.0 - p), seed=seed, offset=offset)
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None, None, None, None
+        mask, = ctx.saved_tensors
+        return _Dropout.apply(gout, mask, None, 0, ctx.p), None, None, None, None
+
+
+_PHILOX = {"offset": 0}
+
+
+def philox_next():
+    """(seed, offset) for the next device-made dropout mask: the seed follows torch's (torch.manual_seed), the offset
+    counts the masks made in this process, so no two masks share their bits."""
+    off = _PHILOX["offset"]
+    _PHILOX["offset"] = off + 1
+    return torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, off
+
+
+def keep_mask(shape, device, p_keep, host):
+    """A uint8 keep mask (1 = keep). host: torch.empty(shape).bernoulli_(p_keep) on the default HOST generator - the
+    reference's draw, consumed identically - moved to `device`; else Philox4x32-10 bits made on the device."""
+    from .layers import to_device_async
+    if host:
+        return to_device_async(torch.empty(tuple(shape)).bernoulli_(p_keep).to(torch.uint8), device)
+    seed, off = philox_next()
+    m = torch.empty(tuple(shape), dtype=torch.uint8, device=device)
+    return K().dropout(None, m, p_keep=p_keep, seed=seed, offset=off)
+
+
+def dropout(x, p=0.5, host=True, mask=None):
+    """nn.Dropout(p) in training mode: x * keep / (1 - p). mask: a uint8 keep mask of x's shape to use; else one is
+    drawn (`host`: on the host generator as the reference draws it; else made on the device in the same launch).
+    -> (y, mask)."""
+    if mask is None and host:
+        mask = keep_mask(x.shape, x.device, 1.0 - p, True)
+    if mask is not None:
+        return _Dropout.apply(x, mask, None, 0, float(p)), mask
+    mask = torch.empty(tuple(x.shape), dtype=torch.uint8, device=x.device)
+    seed, off = philox_next()
+    y = _Dropout.apply(x, mask, seed, off, float(p))
+    return y, mask
