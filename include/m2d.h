@@ -271,6 +271,15 @@ int m2d_gru_stack_counters(int B, int L);
 int m2d_gru_stack_fwd(const float* gi0, const float* const* w_ih_t, const float* const* b_ih,
                       const float* const* w_hh_t, const float* const* b_hh, float* const* out, float* const* saved,
                       const int* lengths, int B, int T, int H, int L, unsigned* counters, void* stream);
+/* m2d_gru_stack_fwd with a carried recurrent state (inference: no backward through h0). h0 (L entries) or NULL:
+ * h0[l] (B, H) is layer l's state before step 0 (a NULL entry: zeros, bit-identical to m2d_gru_stack_fwd); step 0
+ * then computes the full W_hh h0 + b_hh product, in both the per-step and the persistent form. h_n (L entries) or
+ * NULL: h_n[l] (B, H) receives the state after step lengths[b] - 1 (T - 1 without lengths) - torch's h_n. A sequence
+ * split in two calls chained through h_n -> h0 gives the bits of one call over the whole sequence. */
+int m2d_gru_stack_fwd_state(const float* gi0, const float* const* w_ih_t, const float* const* b_ih,
+                            const float* const* w_hh_t, const float* const* b_hh, float* const* out,
+                            float* const* saved, const int* lengths, const float* const* h0, float* const* h_n, int B,
+                            int T, int H, int L, unsigned* counters, void* stream);
 int m2d_gru_persist_error(void);
 /* Recovery from such a timeout without leaving the process: m2d_gru_persist_peek() reads the word without clearing it,
  * m2d_async_fault_word() is the address of its device-memory copy (or NULL; a timed-out launch raises both) - passed to m2d_adam_multi as `skip`, every optimizer
@@ -412,6 +421,10 @@ int m2d_label_embed_bwd(const float* dx, const long long* labels, float* dE, int
    x = NULL: the mask only (gen = 1). */
 int m2d_dropout(const float* x, float* y, unsigned char* mask, long long n, float p_keep, float scale,
                 unsigned long long seed, unsigned long long offset, int gen, void* stream);
+/* out (B, n, C) = standard normals; the value of (b, frame0 + i, c) is a pure function of (seed, b, frame0 + i, c):
+   Philox4x32-10(counter = (c / 4, frame as 64 bits, b), key = seed) followed by Box-Muller. A track's noise is then
+   the same whatever chunks its frames are generated in. */
+int m2d_randn_frames(float* out, unsigned long long seed, long long frame0, int B, int n, int C, void* stream);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,7 @@ SIGNATURES = {
     "m2d_gru_layer_bwd": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _F]),
     "m2d_gru_stack_counters": (_I, [_I, _I]),
     "m2d_gru_stack_fwd": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _F, _F]),
+    "m2d_gru_stack_fwd_state": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _F, _F]),
     "m2d_gru_persist_error": (_I, []),
     "m2d_gru_persist_peek": (_I, []),
     "m2d_async_fault_word": (_c.c_void_p, []),
@@ -97,6 +98,7 @@ SIGNATURES = {
     "m2d_pose_pack3_label": (_I, [_F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _F]),
     "m2d_label_embed_bwd": (_I, [_F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _F]),
     "m2d_dropout": (_I, [_F, _F, _F, _c.c_longlong, _f, _f, _c.c_ulonglong, _c.c_ulonglong, _I, _F]),
+    "m2d_randn_frames": (_I, [_F, _c.c_ulonglong, _c.c_longlong, _I, _I, _I, _F]),
     "m2d_gp_interpolate": (_I, [_F, _F, _F, _F, _I, _I, _F]),
     "m2d_gp_penalty_workspace_bytes": (_S, [_I]),
     "m2d_gp_penalty_fwd": (_I, [_F, _F, _F, _I, _I, _I, _F, _S, _F]),

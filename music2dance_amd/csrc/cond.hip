@@ -3,6 +3,7 @@
 //   * the labelled variant of m2d_pose_pack3: the critic's [interpolated | real | fake] rows with their label channels
 //   * the embedding-table gradient: a fixed-order fp64 sum, one workgroup per (class, column), no atomics
 //   * dropout y = x * keep * scale from a caller's byte mask or from Philox4x32-10 bits made on the device
+//   * standard normals indexed by absolute frame (the streaming generator's noise, phase3/generate.py)
 // Labels are int64 (torch's default index type). A label outside [0, L) never indexes the table: the features it would
 // have selected (forward) or the whole table gradient (backward) become NaN, so the loss shows it.
 #include "m2d_common.h"
@@ -177,6 +178,42 @@ __global__ void __launch_bounds__(256) m2d_dropout_kernel(const float* __restric
   }
 }
 
+// Standard normals indexed by (seed, batch row, ABSOLUTE frame, channel): one Philox4x32-10 call per (b, frame, group
+// of four channels), counter = (c / 4, frame low, frame high, b), key = seed; Box-Muller turns words (0, 1) and (2, 3)
+// into channels 4 j + 0, 1 and 4 j + 2, 3: u1 = ((w >> 8) + 1) 2^-24 in (0, 1], u2 = (w >> 8) 2^-24 in [0, 1),
+// z = sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2). A chunk of frames [frame0, frame0 + n) gets the values a whole-track
+// call gives those frames, whatever the chunking.
+__device__ __forceinline__ void randn_box_muller(unsigned w1, unsigned w2, float& z0, float& z1) {
+  const float u1 = (float)((w1 >> 8) + 1u) * 5.9604644775390625e-8f;
+  const float u2 = (float)(w2 >> 8) * 5.9604644775390625e-8f;
+  const float r = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincosf(6.283185307179586f * u2, &sn, &cs);
+  z0 = r * cs;
+  z1 = r * sn;
+}
+
+__global__ void __launch_bounds__(256) m2d_randn_frames_kernel(float* __restrict__ out, unsigned long long seed,
+                                                               long long frame0, int B, int n, int C) {
+  const int C4 = (C + 3) / 4;
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (long long)B * n * C4) return;
+  const int j = (int)(q % C4);
+  const long long bi = q / C4;  // b * n + i
+  const int i = (int)(bi % n);
+  const int b = (int)(bi / n);
+  const unsigned long long f = (unsigned long long)(frame0 + i);
+  const uint4 w = philox4x32_10(make_uint4((unsigned)j, (unsigned)f, (unsigned)(f >> 32), (unsigned)b),
+                                make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
+  float z[4];
+  randn_box_muller(w.x, w.y, z[0], z[1]);
+  randn_box_muller(w.z, w.w, z[2], z[3]);
+  float* o = out + bi * C;
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+    if (4 * j + m < C) o[4 * j + m] = z[m];
+}
+
 }  // namespace
 
 extern "C" {
@@ -231,6 +268,19 @@ int m2d_dropout(const float* x, float* y, unsigned char* mask, long long n, floa
   hipLaunchKernelGGL(m2d_dropout_kernel, dim3((unsigned)m2d_ceil_div64(n, 1024)), dim3(256), 0, stream, x, y, mask, n,
                      p_keep, scale, seed, offset, gen);
   M2D_CHECK_LAUNCH("m2d_dropout");
+  return M2D_OK;
+}
+
+int m2d_randn_frames(float* out, unsigned long long seed, long long frame0, int B, int n, int C, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!out || B <= 0 || n <= 0 || C <= 0 || frame0 < 0 || frame0 > (1ll << 62))
+    M2D_FAIL(M2D_ERR_ARG, "m2d_randn_frames: bad arguments");
+  const long long threads = (long long)B * n * ((C + 3) / 4);
+  if (m2d_ceil_div64(threads, 256) > 0x7fffffffLL) M2D_FAIL(M2D_ERR_ARG, "m2d_randn_frames: too many draws");
+  M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 4.0 * (double)B * n * C, "randn_frames");
+  hipLaunchKernelGGL(m2d_randn_frames_kernel, dim3((unsigned)m2d_ceil_div64(threads, 256)), dim3(256), 0, stream, out,
+                     seed, frame0, B, n, C);
+  M2D_CHECK_LAUNCH("m2d_randn_frames");
   return M2D_OK;
 }
 

@@ -253,9 +253,26 @@ struct GruStackFwdArgs {
   const float* b_hh[GRU_MAX_LAYERS];
   float* out[GRU_MAX_LAYERS];             // (B, T, H)
   float* saved[GRU_MAX_LAYERS];           // (4, B, T, H): r, z, n, hn; NULL when not saving
+  const float* h0[GRU_MAX_LAYERS];        // (B, H) initial state; NULL: zeros (then step 0 skips W_hh h)
+  float* h_n[GRU_MAX_LAYERS];             // (B, H) state after step lengths[b] - 1 (T - 1); NULL: not written
   const int* lengths;
   int B, T, H, L, d;
 };
+
+// The step after which row b's state is torch's h_n: lengths[b] - 1 (clamped to T - 1), T - 1 without lengths;
+// -1 for an empty row (its h_n is then the initial state, written at step 0).
+__device__ __forceinline__ int gru_last_step(const int* lengths, int b, int T) {
+  return lengths ? min(lengths[b], T) - 1 : T - 1;
+}
+
+// h_n of row b, unit u, given this step's (masked) output h
+__device__ __forceinline__ void gru_put_state(const GruStackFwdArgs& a, int l, int b, int u, int t, float h) {
+  float* hn = a.h_n[l];
+  if (!hn) return;
+  const int last = gru_last_step(a.lengths, b, a.T);
+  if (t == last) hn[(size_t)b * a.H + u] = h;
+  else if (last < 0 && t == 0) hn[(size_t)b * a.H + u] = a.h0[l] ? a.h0[l][(size_t)b * a.H + u] : 0.f;
+}
 
 template <int NB, int NW>
 __device__ __forceinline__ void gru_mac(const float* arow, bool rok, const float* wt, int H, int ncol, int bcol,
@@ -285,6 +302,8 @@ __device__ __forceinline__ void gru_mac(const float* arow, bool rok, const float
 // dependent MFMA chain and the operand burst per wave halve; the step is latency-bound)
 #define GRU_FWD_NW 8
 #define GRU_FWD_MAXB 2  // blocks of 16 k per wave: covers H <= 16 * 8 * 2 = 256
+// kState = false: the stateless kernel (h0 = 0, no h_n) exactly as it was compiled before the carried state existed
+template <bool kState>
 __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_stack_fwd_kernel(const GruStackFwdArgs a) {
   constexpr int NW = GRU_FWD_NW;
   __shared__ float red[NW][4][256];
@@ -304,7 +323,11 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_stack_fwd_kernel(cons
   // Both contractions (hidden: h_l[t-1] W_hh^T, input: h_{l-1}[t] W_ih^T) have K = H. When a
   // wave's share fits one batch (H <= 4 * NW * UN = 256) ALL operand loads of both are
   // issued before the first MFMA: one memory round trip per step instead of two.
-  const bool use_h = t > 0, use_i = l > 0;
+  // with an initial state, step 0 multiplies h0 like any other step (the full W_hh h0 + b_hh product)
+  const float* h0 = kState ? a.h0[l] : nullptr;
+  const bool use_h = t > 0 || h0 != nullptr, use_i = l > 0;
+  const float* hsrc = t > 0 ? a.out[l] + ((size_t)arow * T + (t - 1)) * H
+                            : (h0 ? h0 + (size_t)arow * H : a.out[l] + (size_t)arow * T * H);
   if (H <= 16 * NW * GRU_FWD_MAXB) {
     // K = H in blocks of 16: wave w takes blocks w, w + NW; inside a block lane group q = lane >> 4 owns the four
     // consecutive k = 16 j + 4 q + m (MFMA k-step m multiplies the k's {16 j + m, + 4, + 8, + 12}): ONE 16-byte load
@@ -314,7 +337,7 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_stack_fwd_kernel(cons
     const int q = lane >> 4;
     const bool vec = (H & 3) == 0;
     float ah[GRU_FWD_MAXB][4], ai[GRU_FWD_MAXB][4], bh[GRU_FWD_MAXB][4][3], bi[GRU_FWD_MAXB][4][3];
-    const float* hrow = a.out[l] + ((size_t)arow * T + (use_h ? t - 1 : 0)) * H;
+    const float* hrow = hsrc;
     const float* irow = a.out[use_i ? l - 1 : 0] + ((size_t)arow * T + t) * H;
     const float* wh = a.w_hh_t[l];
     const float* wi = a.w_ih_t[use_i ? l : 0];
@@ -379,7 +402,7 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_stack_fwd_kernel(cons
     if (use_h) {
       f32x4 h3[3] = {acc[0], acc[1], acc[2]};
       const int cols[3] = {0, 1, 2};
-      gru_mac<3, NW>(a.out[l] + ((size_t)arow * T + (t - 1)) * H, rok, a.w_hh_t[l], H, 3 * H, bcol, cok, wave, lane, h3, cols);
+      gru_mac<3, NW>(hsrc, rok, a.w_hh_t[l], H, 3 * H, bcol, cok, wave, lane, h3, cols);
       acc[0] = h3[0]; acc[1] = h3[1]; acc[2] = h3[2];
     }
   }
@@ -413,10 +436,11 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_stack_fwd_kernel(cons
   const float r = gru_sigmoid(gir + s[0] + bh[u]);
   const float z = gru_sigmoid(giz + s[1] + bh[H + u]);
   const float n = tanhf(gin + r * hn);
-  const float hprev = t > 0 ? a.out[l][(bt - 1) * H + u] : 0.f;
+  const float hprev = t > 0 ? a.out[l][(bt - 1) * H + u] : (h0 ? h0[(size_t)b * H + u] : 0.f);
   float h = (1.f - z) * n + z * hprev;
   if (a.lengths && t >= a.lengths[b]) h = 0.f;
   a.out[l][bt * H + u] = h;
+  if (kState) gru_put_state(a, l, b, u, t, h);
   if (a.saved[l]) {
     const size_t plane = (size_t)a.B * T * H;
     float* sv = a.saved[l];
@@ -545,6 +569,7 @@ __device__ __forceinline__ bool gru_spin_operands(bool use_i, __amdgpu_buffer_rs
   }
 }
 
+template <bool kState>
 __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(const GruPersistArgs pa) {
   constexpr int NW = GRU_FWD_NW;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -589,7 +614,9 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(co
   const int row = (tid & 255) >> 4, col = tid & 15;
   const int b = b0 + row, u = u0 + col;
   const bool owner = tid < 256 && b < a.B && u < H;
-  float hprev = 0.f;  // this thread's own previous output (owner threads)
+  // initial state: written before the launch, so it is read with plain loads at step 0 and never waited for
+  const float* h0 = kState ? a.h0[l] : nullptr;
+  float hprev = (owner && h0) ? h0[(size_t)b * H + u] : 0.f;  // this thread's own previous output (owner threads)
   float bhr = 0.f, bhz = 0.f, bhn = 0.f, bir = 0.f, biz = 0.f, bin = 0.f;
   if (owner) {
     bhr = a.b_hh[l][u]; bhz = a.b_hh[l][H + u]; bhn = a.b_hh[l][2 * H + u];
@@ -605,7 +632,7 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(co
     nir = gi[u]; niz = gi[H + u]; nin = gi[2 * H + u];
   }
   for (int t = 0; t < T; ++t) {
-    const bool use_h = t > 0;
+    const bool use_h = t > 0 || h0 != nullptr;
     f32x4 acc[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -617,8 +644,18 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(co
     // ---- operands: step t of the layer below (usually there already) and step t-1 of every hidden tile of this
     //      layer (the critical dependency)
     float ai[GRU_FWD_MAXB][4], ah[GRU_FWD_MAXB][4];
-    if (!gru_spin_operands(use_i, low_rs, a.out[use_i ? l - 1 : l], ((size_t)arow * T + t) * H, use_h, own_rs, a.out[l],
-                           ((size_t)arow * T + (use_h ? t - 1 : 0)) * H, rok, H, nblk, vec, wave, q, pa.error, pa.mirror,
+    if (t == 0 && h0) {
+      // step 0 of a carried state: the same k assignment as gru_load_rows, from h0 (B, H)
+#pragma unroll
+      for (int i = 0; i < GRU_FWD_MAXB; ++i) {
+        const int k0 = 16 * (wave + NW * i) + 4 * q;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+          ah[i][m] = (wave + NW * i < nblk && rok && k0 + m < H) ? h0[(size_t)arow * H + k0 + m] : 0.f;
+      }
+    }
+    if (!gru_spin_operands(use_i, low_rs, a.out[use_i ? l - 1 : l], ((size_t)arow * T + t) * H, t > 0, own_rs, a.out[l],
+                           ((size_t)arow * T + (t > 0 ? t - 1 : 0)) * H, rok, H, nblk, vec, wave, q, pa.error, pa.mirror,
                            pa.spin_limit, ai, ah, spin_acc))
       return;  // timeout or error elsewhere (waves that have left are not counted by the barriers)
     if (use_i) {
@@ -675,6 +712,7 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(co
       if (a.lengths && t >= a.lengths[b]) h = 0.f;
       hprev = h;
       gru_st_sc1(a.out[l] + bt_ * H + u, h);  // published: consumers spin on the value itself
+      if (kState) gru_put_state(a, l, b, u, t, h);
       if (a.saved[l]) {
         const size_t plane = (size_t)a.B * T * H;
         float* sv = a.saved[l];
@@ -978,7 +1016,9 @@ static GruPersistState* gru_persist_state() {
     if (hipMalloc((void**)&ps.mirror, 64) != hipSuccess || hipMemset(ps.mirror, 0, 64) != hipSuccess) return &ps;
     // ~0.4 us per poll with s_sleep(4): 2^21 polls ~ 1 s before a workgroup gives up
     ps.spin_limit = 1u << 21;
-    if (hipFuncSetAttribute((const void*)m2d_gru_persist_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)m2d_gru_persist_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            140 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)m2d_gru_persist_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             140 * 1024) != hipSuccess)
       return &ps;
     if (hipFuncSetAttribute((const void*)m2d_gru_persist_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1011,20 +1051,27 @@ extern "C" {
 // scratch words m2d_gru_stack_fwd needs for its persistent form (multiple of 4: the memset stays 16-byte sized)
 int m2d_gru_stack_counters(int B, int L) { return L * m2d_ceil_div(B, 16) * GRU_CNT_STRIDE; }
 
+}  // extern "C"
+
 // L-layer GRU forward on the (layer, t) diagonal. Pointer arrays have L entries; entry 0 of
 // w_ih_t / b_ih is ignored (layer 0's projection gi0 is precomputed by m2d_gemm).
 // saved[l]: (4, B, T, H) or all NULL.
-int m2d_gru_stack_fwd(const float* gi0, const float* const* w_ih_t, const float* const* b_ih,
-                      const float* const* w_hh_t, const float* const* b_hh, float* const* out, float* const* saved,
-                      const int* lengths, int B, int T, int H, int L, unsigned* counters, void* stream_) {
+static int gru_stack_fwd(const char* name, const float* gi0, const float* const* w_ih_t, const float* const* b_ih,
+                         const float* const* w_hh_t, const float* const* b_hh, float* const* out, float* const* saved,
+                         const int* lengths, const float* const* h0, float* const* h_n, int B, int T, int H, int L,
+                         unsigned* counters, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (B <= 0 || T <= 0 || H <= 0 || L <= 0 || L > GRU_MAX_LAYERS) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_stack_fwd: bad shape");
+  if (B <= 0 || T <= 0 || H <= 0 || L <= 0 || L > GRU_MAX_LAYERS) M2D_FAIL(M2D_ERR_ARG, "%s: bad shape", name);
   GruStackFwdArgs a;
   memset(&a, 0, sizeof(a));
   a.gi0 = gi0; a.lengths = lengths;
+  bool state = false;  // any initial or final state: the kState instantiations
   for (int l = 0; l < L; ++l) {
     a.w_ih_t[l] = w_ih_t[l]; a.b_ih[l] = b_ih[l]; a.w_hh_t[l] = w_hh_t[l]; a.b_hh[l] = b_hh[l];
     a.out[l] = out[l]; a.saved[l] = saved ? saved[l] : nullptr;
+    a.h0[l] = h0 ? h0[l] : nullptr;
+    a.h_n[l] = h_n ? h_n[l] : nullptr;
+    state = state || a.h0[l] || a.h_n[l];
   }
   a.B = B; a.T = T; a.H = H; a.L = L;
   dim3 grid(m2d_ceil_div(H, 16), m2d_ceil_div(B, 16), L);
@@ -1049,7 +1096,10 @@ int m2d_gru_stack_fwd(const float* gi0, const float* const* w_ih_t, const float*
         pa.error = ps->error_dev;
       pa.mirror = ps->mirror;
         pa.spin_limit = ps->spin_limit;
-        hipLaunchKernelGGL(m2d_gru_persist_fwd_kernel, grid, dim3(64 * GRU_FWD_NW), gru_persist_lds(H), stream, pa);
+        if (state)
+          hipLaunchKernelGGL(m2d_gru_persist_fwd_kernel<true>, grid, dim3(64 * GRU_FWD_NW), gru_persist_lds(H), stream, pa);
+        else
+          hipLaunchKernelGGL(m2d_gru_persist_fwd_kernel<false>, grid, dim3(64 * GRU_FWD_NW), gru_persist_lds(H), stream, pa);
         M2D_CHECK_LAUNCH("m2d_gru_persist_fwd_kernel");
         return M2D_OK;
       }
@@ -1057,10 +1107,34 @@ int m2d_gru_stack_fwd(const float* gi0, const float* const* w_ih_t, const float*
   }
   for (int d = 0; d < T + L - 1; ++d) {
     a.d = d;
-    hipLaunchKernelGGL(m2d_gru_stack_fwd_kernel, grid, dim3(64 * GRU_FWD_NW), 0, stream, a);
+    if (state)
+      hipLaunchKernelGGL(m2d_gru_stack_fwd_kernel<true>, grid, dim3(64 * GRU_FWD_NW), 0, stream, a);
+    else
+      hipLaunchKernelGGL(m2d_gru_stack_fwd_kernel<false>, grid, dim3(64 * GRU_FWD_NW), 0, stream, a);
   }
   M2D_CHECK_LAUNCH("m2d_gru_stack_fwd_kernel");
   return M2D_OK;
+}
+
+extern "C" {
+
+int m2d_gru_stack_fwd(const float* gi0, const float* const* w_ih_t, const float* const* b_ih,
+                      const float* const* w_hh_t, const float* const* b_hh, float* const* out, float* const* saved,
+                      const int* lengths, int B, int T, int H, int L, unsigned* counters, void* stream_) {
+  return gru_stack_fwd("m2d_gru_stack_fwd", gi0, w_ih_t, b_ih, w_hh_t, b_hh, out, saved, lengths, nullptr, nullptr, B,
+                       T, H, L, counters, stream_);
+}
+
+// m2d_gru_stack_fwd with a carried state: h0[l] (B, H) or NULL (zeros; h0 itself may be NULL), h_n[l] (B, H) or NULL
+// receives the state after step lengths[b] - 1 (T - 1 without lengths). A chunked sequence chained through
+// h_n -> h0 gives the bits of one call over the whole sequence.
+int m2d_gru_stack_fwd_state(const float* gi0, const float* const* w_ih_t, const float* const* b_ih,
+                            const float* const* w_hh_t, const float* const* b_hh, float* const* out,
+                            float* const* saved, const int* lengths, const float* const* h0, float* const* h_n, int B,
+                            int T, int H, int L, unsigned* counters, void* stream_) {
+  if (L > GRU_MAX_LAYERS && h0) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_stack_fwd_state: an initial state needs L <= %d", GRU_MAX_LAYERS);
+  return gru_stack_fwd("m2d_gru_stack_fwd_state", gi0, w_ih_t, b_ih, w_hh_t, b_hh, out, saved, lengths, h0, h_n, B, T,
+                       H, L, counters, stream_);
 }
 
 // 1 when a persistent GRU launch timed out since the last call (and clears the flag): the outputs

@@ -945,27 +945,43 @@ class HipKernels:
         arr = (ctypes.c_void_p * len(tensors))(*[_ptr(t) for t in tensors])
         return arr, ctypes.cast(arr, ctypes.c_void_p)
 
-    def gru_stack_fwd(self, gi0, w_ih_t, b_ih, w_hh_t, b_hh, lengths=None, save=True, persistent=True):
+    def gru_stack_fwd(self, gi0, w_ih_t, b_ih, w_hh_t, b_hh, lengths=None, save=True, persistent=True, h0=None,
+                      want_state=False):
         """L-layer GRU on the (layer, t) diagonal. Lists have L entries (entry 0 of w_ih_t / b_ih may
-        be None). Returns ([out_l (B,T,H)], [saved_l (4,B,T,H)] or None)."""
+        be None). Returns ([out_l (B,T,H)], [saved_l (4,B,T,H)] or None).
+        h0: the initial state, (L, B, H) or a list of L (B, H) tensors (None: zeros); want_state: also return h_n
+        (L, B, H), the state after step lengths[b] - 1 (T - 1 without lengths) -> (outs, saved, h_n)."""
         L = len(w_hh_t)
         dev = _chk(gi0, *[t for t in list(w_ih_t) + list(b_ih) + list(w_hh_t) + list(b_hh) if t is not None])
         B, T, H3 = gi0.shape
         H = H3 // 3
+        state = h0 is not None or want_state
+        if h0 is not None:
+            h0 = list(h0)
+            if len(h0) != L or any(tuple(t.shape) != (B, H) for t in h0) or _chk(*h0) != dev:
+                raise _lib.M2dError("GRU h0: %d layers of (%d, %d) on %s expected" % (L, B, H, dev))
         # (one allocation: the persistent launch pre-fills every layer's output with its hand-off sentinel in one memset)
         outs = list(torch.empty((L, B, T, H), dtype=torch.float32, device=dev).unbind(0))
         saved = [torch.empty((4, B, T, H), dtype=torch.float32, device=dev) for _ in range(L)] if save else None
+        h_n = torch.empty((L, B, H), dtype=torch.float32, device=dev) if want_state else None
         keep = [self._ptr_array(v) for v in (w_ih_t, b_ih, w_hh_t, b_hh, outs)]
         sv = self._ptr_array(saved) if save else (None, None)
+        hz = self._ptr_array(h0) if h0 is not None else (None, None)
+        hn = self._ptr_array(list(h_n.unbind(0))) if want_state else (None, None)
         h = _lib.lib()
         # scratch for the persistent form (one launch for the whole recurrence); the library decides
         counters = (torch.empty((h.m2d_gru_stack_counters(B, L),), dtype=torch.int32, device=dev)
                     if (persistent and self.persistent_gru) else None)
         with _on(dev):
-            rc = h.m2d_gru_stack_fwd(_ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
-                                     sv[1], _ptr(lengths), B, T, H, L, _ptr(counters), _stream(dev))
-        _lib.check(rc, "m2d_gru_stack_fwd")
-        return outs, saved
+            if state:
+                rc = h.m2d_gru_stack_fwd_state(_ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
+                                               sv[1], _ptr(lengths), hz[1], hn[1], B, T, H, L, _ptr(counters),
+                                               _stream(dev))
+            else:
+                rc = h.m2d_gru_stack_fwd(_ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
+                                         sv[1], _ptr(lengths), B, T, H, L, _ptr(counters), _stream(dev))
+        _lib.check(rc, "m2d_gru_stack_fwd_state" if state else "m2d_gru_stack_fwd")
+        return (outs, saved, h_n) if want_state else (outs, saved)
 
     @staticmethod
     def check_async_errors():
@@ -1202,6 +1218,18 @@ class HipKernels:
             rc = _lib.lib().m2d_label_embed_bwd(_ptr(dx), _ptr(labels), _ptr(o), int(r0), int(r1), T, Ctot, int(c0),
                                                 int(L), int(D), int(layout), _stream(dev))
         _lib.check(rc, "m2d_label_embed_bwd")
+        return o
+
+    def randn_frames(self, seed, frame0, B, n, C, device, out=None):
+        """(B, n, C) standard normals; entry (b, i, c) is a pure function of (seed, b, frame0 + i, c) (m2d_randn_frames)"""
+        o = torch.empty((B, n, C), dtype=torch.float32, device=device) if out is None else out
+        dev = _chk(o)
+        if tuple(o.shape) != (B, n, C) or o.dtype != torch.float32 or not o.is_contiguous():
+            raise _lib.M2dError("randn_frames: out must be a contiguous float32 (%d, %d, %d) tensor" % (B, n, C))
+        with _on(dev):
+            rc = _lib.lib().m2d_randn_frames(_ptr(o), int(seed) & 0xFFFFFFFFFFFFFFFF, int(frame0), int(B), int(n),
+                                             int(C), _stream(dev))
+        _lib.check(rc, "m2d_randn_frames")
         return o
 
     def dropout(self, x, mask, p_keep=0.5, scale=2.0, seed=None, offset=0, out=None):

@@ -163,13 +163,19 @@ class GRU(nn.GRU):
     tensor plus optional per-sequence lengths (the reference's packed input with equal
     lengths is bit-identical to the dense one)."""
 
-    def forward(self, x, lengths=None):
+    def forward(self, x, lengths=None, hx=None):
+        """-> (out, None); with hx (num_layers, B, H), the carried initial state: (out, h_n) in torch's layout,
+        h_n the state after step lengths[b] - 1 (inference only, stacks of at most 4 layers)."""
         if not self.batch_first or self.bidirectional or self.dropout != 0.0 or not self.bias:
             raise NotImplementedError("m2d GRU: only batch_first / unidirectional / no-dropout is supported")
         params = []
         for layer in range(self.num_layers):
             params += [getattr(self, "weight_ih_l%d" % layer), getattr(self, "weight_hh_l%d" % layer),
                        getattr(self, "bias_ih_l%d" % layer), getattr(self, "bias_hh_l%d" % layer)]
+        if hx is not None:
+            if self.num_layers > 4:
+                raise NotImplementedError("m2d GRU: an initial state needs at most 4 layers (got %d)" % self.num_layers)
+            return ops.gru_stack(x, params, lengths, hx=hx, return_state=True)
         if self.num_layers <= 4:
             # every layer on the (layer, t) diagonal: T + L - 1 dependent launches instead of L * T
             return ops.gru_stack(x, params, lengths), None

@@ -659,10 +659,36 @@ class _GRUStack(Function):
         return (dx, None, None) + tuple(grads)
 
 
-def gru_stack(x, params, lengths=None):
-    """nn.GRU(batch_first, h0 = 0) with len(params) // 4 layers; params = [w_ih, w_hh, b_ih, b_hh] per layer."""
-    save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-    return _GRUStack.apply(x, lengths, save, *params)
+def gru_stack(x, params, lengths=None, hx=None, return_state=False):
+    """nn.GRU(batch_first) with len(params) // 4 layers; params = [w_ih, w_hh, b_ih, b_hh] per layer.
+    hx: the initial state (L, B, H) (None: zeros); return_state: -> (out, h_n (L, B, H)), h_n being the state after
+    step lengths[b] - 1 (T - 1 without lengths). With either, the call is inference only: there is no backward through
+    a carried state, so a graph that would need one is refused."""
+    if hx is None and not return_state:
+        save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+        return _GRUStack.apply(x, lengths, save, *params)
+    if torch.is_grad_enabled():
+        if hx is not None and hx.requires_grad:
+            raise RuntimeError("gru_stack: gradients through the initial state hx are not implemented "
+                               "(detach it or run under torch.no_grad())")
+        if x.requires_grad or any(p.requires_grad for p in params):
+            raise RuntimeError("gru_stack: a carried state is inference only - run under torch.no_grad()")
+    L = len(params) // 4
+    w_ih = [_c(params[4 * l]) for l in range(L)]
+    w_hh = [_c(params[4 * l + 1]) for l in range(L)]
+    b_ih = [_c(params[4 * l + 2]) for l in range(L)]
+    b_hh = [_c(params[4 * l + 3]) for l in range(L)]
+    x = _c(x)
+    B, T, I = x.shape
+    H = w_hh[0].shape[1]
+    if hx is not None and tuple(hx.shape) != (L, B, H):
+        raise ValueError("gru_stack: hx of shape %s, (%d, %d, %d) expected" % (tuple(hx.shape), L, B, H))
+    k = K()
+    gi0 = k.gemm(0, x.view(B * T, I), w_ih[0], b_ih[0]).view(B, T, 3 * H)
+    outs, _, h_n = k.gru_stack_fwd(gi0, [None] + [k.transposed(w) for w in w_ih[1:]], [None] + b_ih[1:],
+                                   [k.transposed(w) for w in w_hh], b_hh, lengths, save=False,
+                                   h0=None if hx is None else _c(hx), want_state=True)
+    return (outs[-1], h_n) if return_state else outs[-1]
 
 
 def gru_layer(x, w_ih, w_hh, b_ih, b_hh, lengths=None):

@@ -344,6 +344,34 @@ class SequenceGenerator(nn.Module):
         latent = torch.cat((h, n), -1)
         return self.decoder(latent.reshape(-1, self.decoder.latent_size))
 
+    @torch.no_grad()
+    def step(self, x, state=None, noise=None):
+        """One chunk of a longer track (eval mode only): -> (rows (B * k, output_size), state).
+        x: the chunk's k audio windows, (B, k, window) as a window view of the track (read in place) or dense, or a
+        layers.WindowView; state: what the previous chunk returned - (audio GRU state (n_cells, B, H), noise GRU state
+        (1, B, noise_size)) - or None at the start of the track; noise: (B, k, noise_size), host-drawn when None.
+        In eval mode BatchNorm uses its running statistics, so no row depends on another: chunks chained through
+        `state` give the rows of one call over the whole track."""
+        if self.training:
+            raise RuntimeError("SequenceGenerator.step needs eval mode: in training mode batch statistics couple the rows")
+        if isinstance(x, WindowView):
+            wv, frames = x, x.T
+        else:
+            frames = x.size(1)
+            wv = WindowView.of(x) if (x.is_cuda and x.size(2) == self.window_size) else None
+        enc_in = wv if wv is not None else x.reshape(-1, 1, self.window_size)
+        code = self.audio_enc(enc_in).view(-1, frames, self.input_size)
+        B = code.shape[0]
+        if noise is None:
+            noise = to_device_async(torch.randn(B, frames, self.noise_size), code.device)
+        if state is None:
+            rnn = self.audio_rnn.rnn
+            state = (code.new_zeros(rnn.num_layers, B, rnn.hidden_size), code.new_zeros(1, B, self.noise_size))
+        h, audio_state = self.audio_rnn.rnn(code, None, state[0])
+        n, noise_state = self.noise_gen.rnn(noise.contiguous(), None, state[1])
+        latent = torch.cat((h, n), -1)
+        return self.decoder(latent.reshape(-1, self.decoder.latent_size)), (audio_state, noise_state)
+
     # -- the audio path of a forward, kept for a second forward of the SAME batch through the SAME weights --------------
     # The reference's loop body that holds a generator iteration runs the generator twice on one batch: once for the
     # critic iteration (phase3/train.py:195, graph built and dropped) and once for the generator iteration (:222), with
