@@ -426,6 +426,16 @@ int m2d_dropout(const float* x, float* y, unsigned char* mask, long long n, floa
    the same whatever chunks its frames are generated in. */
 int m2d_randn_frames(float* out, unsigned long long seed, long long frame0, int B, int n, int C, void* stream);
 
+/* ---- stick-figure video frames (visualize.py:195-255: draw, frame_to_vid) ------------------------------------------
+ * poses (n_frames, 69) fp32, world coordinates (joint j = (x, y, z) at 3j..3j+2; z unused) -> out (n_frames, height,
+ * width, 3) uint8 RGB, every byte written: white, with 23 disks (radius 4) and 21 segments (width 3) in blue
+ * (0, 0, 255), the reference's skeleton. x' = fl32(x + width/2), y' = fl32(y + height/2); pixel (trunc(x'), trunc(y')),
+ * a midpoint trunc(fl32(fl32(a' + b') * 0.5)); image row = height - 1 - pixel height. A joint with a non-finite
+ * coordinate or |x'| or |y'| >= 2^14 draws nothing, nor does any segment that uses it. Coverage is exact in integers:
+ * a disk covers (c - px)^2 + (r - py)^2 <= 16, a segment the pixels at squared distance <= 1.
+ * height, width in [1, 4096]; n_frames 0: nothing to do. Deterministic, no atomics. */
+int m2d_render_sticks(const float* poses, long n_frames, int height, int width, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

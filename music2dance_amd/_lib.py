@@ -99,6 +99,7 @@ SIGNATURES = {
     "m2d_label_embed_bwd": (_I, [_F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _F]),
     "m2d_dropout": (_I, [_F, _F, _F, _c.c_longlong, _f, _f, _c.c_ulonglong, _c.c_ulonglong, _I, _F]),
     "m2d_randn_frames": (_I, [_F, _c.c_ulonglong, _c.c_longlong, _I, _I, _I, _F]),
+    "m2d_render_sticks": (_I, [_F, _L, _I, _I, _F, _F]),
     "m2d_gp_interpolate": (_I, [_F, _F, _F, _F, _I, _I, _F]),
     "m2d_gp_penalty_workspace_bytes": (_S, [_I]),
     "m2d_gp_penalty_fwd": (_I, [_F, _F, _F, _I, _I, _I, _F, _S, _F]),

@@ -1232,6 +1232,24 @@ class HipKernels:
         _lib.check(rc, "m2d_randn_frames")
         return o
 
+    def render_sticks(self, poses, height, width, out=None):
+        """poses (n, 69) or (n, 23, 3) fp32 -> (n, height, width, 3) uint8 RGB stick figures (m2d_render_sticks)"""
+        dev = _chk(poses)
+        if poses.dim() not in (2, 3) or tuple(poses.shape[1:]) not in ((69,), (23, 3)):
+            raise _lib.M2dError("render_sticks: poses must be (n, 69) or (n, 23, 3), got %s" % (tuple(poses.shape),))
+        if not (1 <= int(height) <= 4096 and 1 <= int(width) <= 4096):
+            raise _lib.M2dError("render_sticks: height and width must lie in [1, 4096], got %d x %d" % (height, width))
+        n = poses.shape[0]
+        shape = (n, int(height), int(width), 3)
+        o = torch.empty(shape, dtype=torch.uint8, device=dev) if out is None else out
+        if (not o.is_cuda or o.device != dev or o.dtype != torch.uint8 or tuple(o.shape) != shape
+                or not o.is_contiguous()):
+            raise _lib.M2dError("render_sticks: out must be a contiguous uint8 %s tensor on %s" % (shape, dev))
+        with _on(dev):
+            rc = _lib.lib().m2d_render_sticks(_ptr(poses), n, int(height), int(width), _ptr(o), _stream(dev))
+        _lib.check(rc, "m2d_render_sticks")
+        return o
+
     def dropout(self, x, mask, p_keep=0.5, scale=2.0, seed=None, offset=0, out=None):
         """y = x * keep * scale. seed None: keep from the uint8 `mask` (the caller's); else Philox4x32-10 bits of
         (seed, offset, index), written into `mask` when given. x None: the mask only. -> y (or mask)."""

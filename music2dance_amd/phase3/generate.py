@@ -2,7 +2,7 @@
 
     python -m music2dance_amd.phase3.generate -c music2dance_amd/phase3/configs/default.yaml -l <logdir> \
         [--gen-weights PATH] (--audio a.wav [b.wav ...] | --val | --synthetic) [--chunk-frames N] [--seed S] \
-        [--folder DIR] [-d N]
+        [--folder DIR] [-d N] [--video]
 
 The reference generates a 30-second sample in phase3/test.py:64-72 (with a broken call) and says its generator
 handles tracks of any length. Frame t of a track reads the audio window track[t hop - left, t hop - left + window)
@@ -16,7 +16,9 @@ drawn on the device per absolute frame index (m2d_randn_frames): a seed gives th
 Outputs: <logdir>/samples/<name>.npy, the inverse-MinMax-scaled poses (T, 23, 3) of each track (what the reference's
 visualize.frame_to_vid takes), and <logdir>/samples/generation.json (strict JSON): per track the frame count, the
 seconds of audio, the chunk size, the wall time, the GPU time per chunk (p50 / p99) and the real-time factor
-(seconds of audio per second of wall time).
+(seconds of audio per second of wall time). With --video each saved array is also rendered to
+<logdir>/samples/<name>.avi (visualize.frame_to_vid at the config's video_rate), and its track entry gains `video`,
+`render_ms` (device time of the render launches) and `video_s` (wall time of the whole write).
 """
 import argparse
 import json
@@ -156,6 +158,8 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="noise seed")
     ap.add_argument("--folder", type=str, default=None, help="dataset folder (overrides the YAML's `folder:`)")
     ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
+    ap.add_argument("--video", action="store_true", help="also render each saved dance to <logdir>/samples/<name>.avi "
+                                                         "(300 x 300 stick figures at the config's video_rate)")
     return ap.parse_args(argv)
 
 
@@ -265,11 +269,17 @@ def generate(opts, cfg, device):
         poses, timing = run_track(gen, audio, opts.seed, window, hop, pad, opts.chunk_frames)
         assert poses.shape[0] == T, (poses.shape, T)
         arr = scaler.inverse_transform(poses.cpu().numpy().astype(np.float64)).astype(np.float32)
-        np.save(os.path.join(outdir, name + ".npy"), arr.reshape(T, STICK_CHANNELS // 3, 3))
+        saved = arr.reshape(T, STICK_CHANNELS // 3, 3)
+        np.save(os.path.join(outdir, name + ".npy"), saved)
         seconds = audio.shape[0] / float(rate)
         res["tracks"].append(dict(name=name, frames=T, seconds=seconds, chunk_frames=int(opts.chunk_frames),
                                   real_time_factor=seconds / timing["wall_s"] if timing["wall_s"] > 0 else None,
                                   **timing))
+        if getattr(opts, "video", False):
+            from .. import visualize
+            path = os.path.join(outdir, name + ".avi")
+            vid = visualize.frame_to_vid(saved, path, ds["video_rate"])
+            res["tracks"][-1].update(video=path, render_ms=vid["render_ms"], video_s=vid["wall_s"])
     with open(os.path.join(outdir, "generation.json"), "w") as f:
         json.dump(json_safe(res), f, indent=1, allow_nan=False)
     return res
