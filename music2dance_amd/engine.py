@@ -134,6 +134,11 @@ class WganGpEngine:
         self._arm_keep = False     # set by train_step for the body that holds a generator iteration
         self._gen_epoch = 0        # bumped by every generator optimizer step (fused steps do not move version counters)
         self._kept_key = None
+        # captured-graph mode (enable_graphs): graphs per input shape, and the count of async-fault recoveries of the
+        # process as of the last _check_async - graphs are only ever captured right after one (train_step)
+        self._use_graphs = False
+        self._graphs = {}
+        self._graphs_gen = int(getattr(k, "async_faults", 0))
 
     # -- critic optimiser step, possibly deferred so its all-reduce overlaps the next G forward
     def _finish_critic_step(self):
@@ -275,7 +280,7 @@ class WganGpEngine:
         # (with their private scratch, which a killed launch may have left non-zero); the next train_step re-captures,
         # now with per-step recurrent launches.
         gen = int(getattr(k, "async_faults", 0))
-        if getattr(self, "_graphs", None) and getattr(self, "_graphs_gen", gen) != gen:
+        if self._graphs and self._graphs_gen != gen:
             self._graphs = {}
         self._graphs_gen = gen
 
@@ -285,9 +290,18 @@ class WganGpEngine:
         inputs_ready: optional event after which the batch tensors are complete; lets the generator
         forward start before the previous iteration has drained (_generator_forward_nograd)."""
         self.total_iterations += 1
-        self._inputs_ready = inputs_ready
-        self._check_async()
         with_gen = self.total_iterations % self.n_critic_steps == 0
+        eager = not self._use_graphs or batch[0].device.type != "cuda"
+        if eager:
+            # (a replay reads static buffers that this call fills on the main stream: it has no use for the event)
+            self._inputs_ready = inputs_ready
+        self._check_async()
+        out = self._eager_step(batch, with_gen) if eager else self._graph_step(batch, with_gen)
+        self.last = out
+        self.last_full.update(out)
+        return out
+
+    def _eager_step(self, batch, with_gen):
         # this body's critic iteration may keep the generator's audio path for the generator iteration that follows IN
         # THIS CALL (Phase3Engine.reuse_audio_path): armed here and nowhere else - callers that drive critic_iteration /
         # generator_iteration themselves never keep anything (ADVICE r5: inferring it from total_iterations made every
@@ -301,9 +315,118 @@ class WganGpEngine:
                     out.update(self.generator_iteration(*batch))
         finally:
             self._arm_keep = False
-        self.last = out
-        self.last_full.update(out)
         return out
+
+    def _step_schedulers(self):
+        """After every generator optimizer step, eager or replayed (phase 2 steps its learning-rate schedulers here)."""
+
+    # ------------------------------------------------------------------ captured-graph mode
+    def enable_graphs(self, on=True):
+        """Replay each loop body's forward / backward as one captured HIP graph (per input shape), which takes the
+        host's launch rate off the critical path. The optimizer (and scheduler) steps and the data-parallel gradient
+        exchange stay eager. The random draws the reference makes inside the loop are made on the host generator where
+        the eager path makes them, in the same order, before each replay and fed through static buffers, so results
+        equal the eager path's (tests/test_critic_step.py, tests/test_gpu_full_size.py).
+
+        The mechanism (train_step -> _graph_step, _graph_for) is shared; an engine supplies `_graph_bodies` (static
+        buffers and the bodies to capture), `_feed_critic` / `_feed_generator` (what it copies and draws before the
+        critic / generator replay), and where needed `_graph_key` and `_step_schedulers`. What each phase gains from
+        it is measured in the docstring of its `_graph_bodies`."""
+        self._use_graphs = bool(on)
+        self._graphs = {}
+        if on and hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
+            # warm-up and capture run on side streams by design
+            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
+        return self
+
+    def _graph_key(self, real, *rest):
+        return tuple(real.shape)
+
+    def _graph_bodies(self, *batch):
+        """-> (g, bodies) for the shape of `batch`. g: a dict with the static buffers the bodies read (filled by
+        _feed_critic / _feed_generator before each replay). bodies: [(name, fn, pool_of, grads_of)] in launch order,
+        the names "critic" and "gen" among them: fn() is captured as graph g[name], its result kept as g[name + "_out"];
+        pool_of names an EARLIER body whose memory pool this graph shares (None: a pool of its own - required for a
+        graph that replays while another one runs); grads_of is the module whose .grad tensors the body produces
+        (kept as g[name + "_grads"]) or None."""
+        raise NotImplementedError("%s has no captured-graph mode" % type(self).__name__)
+
+    def _feed_critic(self, g, *batch):
+        """Before the critic replay: copy the batch into g's static buffers and make the critic iteration's host draws,
+        in the reference's order."""
+        raise NotImplementedError
+
+    def _feed_generator(self, g, *batch):
+        """Before the generator replay (the batch is already in place): the generator iteration's host draws."""
+        raise NotImplementedError
+
+    @staticmethod
+    def _bind_grads(module, grads):
+        for p, gr in zip(module.parameters(), grads):
+            p.grad = gr
+
+    def _graph_step(self, batch, with_gen):
+        self._finish_critic_step()
+        g = self._graph_for(batch)
+        self._feed_critic(g, *batch)
+        # every captured graph writes its gradients into the tensors it was captured with
+        self._bind_grads(self.critic, g["critic_grads"])
+        g["critic"].replay()
+        self._begin_critic_step()
+        out = dict(g["critic_out"])
+        if with_gen:
+            self._finish_critic_step()
+            self._feed_generator(g, *batch)
+            self._bind_grads(self.gen, g["gen_grads"])
+            g["gen"].replay()
+            self._gen_step()
+            self._step_schedulers()
+            out.update(g["gen_out"])
+        return out
+
+    def _graph_for(self, batch):
+        key = self._graph_key(*batch)
+        g = self._graphs.get(key)
+        if g is not None:
+            return g
+        dev = batch[0].device
+        g, bodies = self._graph_bodies(*batch)
+        # One warm-up pass of each body on a side stream (lazy module loads and allocator growth
+        # must not happen inside a capture); it must leave no trace: the BatchNorm buffers it
+        # touches are restored, gradients are dropped, no optimizer step is taken, no host draw.
+        mods = [self.gen, self.critic]
+        saved = [[b.clone() for b in m.buffers()] for m in mods]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        # (the warm-up backward must not feed the data-parallel exchange either: no start() follows it)
+        quiet = [x.suspended() for x in (self.x_critic, self.x_gen) if x is not None]
+        with torch.cuda.stream(side), contextlib.ExitStack() as es:
+            for q in quiet:
+                es.enter_context(q)
+            for _, fn, _, _ in bodies:
+                fn()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.optim_critic.zero_grad(set_to_none=True)
+        self.optim_gen.zero_grad(set_to_none=True)
+        g["keep"] = []
+        for name, fn, pool_of, grads_of in bodies:
+            g[name] = torch.cuda.CUDAGraph()
+            # graphs that share a pool reuse each other's freed intermediates, which is only safe when they never
+            # overlap: the generator graph takes the critic graph's pool, a graph that replays beside another does not
+            pool = g[pool_of].pool() if pool_of is not None else None
+            g[name + "_out"] = _capture(g[name], fn, dev, g["keep"], pool=pool)
+            if grads_of is not None:
+                # the gradient tensors live in this graph's private pool: a graph captured later for another
+                # shape allocates its own, so each replay re-binds p.grad to the set it writes
+                g[name + "_grads"] = [p.grad for p in grads_of.parameters()]
+        with torch.no_grad():
+            for m, bufs in zip(mods, saved):
+                for b, v in zip(m.buffers(), bufs):
+                    b.copy_(v)
+        torch.cuda.synchronize(dev)
+        self._graphs[key] = g
+        return g
 
 
 # =========================================================================================== phase 3
@@ -453,66 +576,16 @@ class Phase3Engine(WganGpEngine):
             err_gen.backward()
         return {"loss_gen": err_gen.detach(), "l1_loss_train": err_l1.detach()}
 
-    # ------------------------------------------------------------------ captured-graph mode
-    def enable_graphs(self, on=True):
-        """Replay each loop body's forward / backward as one captured HIP graph (per input shape):
-        ~680 kernel launches become one graph launch, which takes the host off the critical path.
-        (Measured on the MI355X host: batch 8, 8.5 ms per body eager -> 5.9 ms replayed; at batch 64 the eager
-        path is GPU-bound and, with the generator forward pipelined one iteration ahead, faster than
-        the single-queue replay - 15.0 vs 16.5 ms - so this is off by default: it is for small
-        batches and slow hosts.)
-        The optimizer steps and the data-parallel gradient exchange stay eager. The random draws
-        the reference makes inside the loop (generator noise, interpolation weights) are made on
-        the host generator in the same order before each replay and fed through static buffers,
-        so results equal the eager path's."""
-        self._use_graphs = bool(on)
-        self._graphs = {}
-        if on and hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
-            # warm-up and capture run on side streams by design
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        return self
+    # ------------------------------------------------------------------ captured-graph mode (WganGpEngine.enable_graphs)
+    def _graph_key(self, real, audio, audio_slices):
+        return (tuple(real.shape), tuple(audio.shape), tuple(audio_slices.shape))
 
-    def train_step(self, real, audio, audio_slices, inputs_ready=None):
-        if not getattr(self, "_use_graphs", False) or real.device.type != "cuda":
-            return super().train_step(real, audio, audio_slices, inputs_ready=inputs_ready)
-        self.total_iterations += 1
-        self._check_async()
-        self._finish_critic_step()
-        g = self._graph_for(real, audio, audio_slices)
-        B, T = self._shapes(real)
-        nz = self.gen.noise_size
-        g["real"].copy_(real.reshape(g["real"].shape))
-        g["audio"].copy_(audio)
-        g["slices"].copy_(audio_slices)
-        # host draws in the reference's order: generator noise, then the penalty's alpha
-        g["noise_c"].copy_(to_device_async(torch.randn(B, T, nz), real.device))
-        g["alpha"].copy_(to_device_async(torch.rand(B, 1), real.device))
-        # every captured graph writes its gradients into the tensors it was captured with
-        self._bind_grads(self.critic, g["critic_grads"])
-        g["critic"].replay()
-        self._begin_critic_step()
-        out = dict(g["critic_out"])
-        if self.total_iterations % self.n_critic_steps == 0:
-            self._finish_critic_step()
-            g["noise_g"].copy_(to_device_async(torch.randn(B, T, nz), real.device))
-            self._bind_grads(self.gen, g["gen_grads"])
-            g["gen"].replay()
-            self._gen_step()
-            out.update(g["gen_out"])
-        self.last = out
-        self.last_full.update(out)
-        return out
-
-    @staticmethod
-    def _bind_grads(module, grads):
-        for p, gr in zip(module.parameters(), grads):
-            p.grad = gr
-
-    def _graph_for(self, real, audio, audio_slices):
-        key = (tuple(real.shape), tuple(audio.shape), tuple(audio_slices.shape))
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
+    def _graph_bodies(self, real, audio, audio_slices):
+        """~680 kernel launches become one graph launch per body. (Measured on the MI355X host: batch 8, 8.5 ms per
+        body eager -> 5.9 ms replayed; at batch 64 the eager path is GPU-bound and, with the generator forward
+        pipelined one iteration ahead, faster than the single-queue replay - 15.0 vs 16.5 ms - so this is off by
+        default: it is for small batches and slow hosts.) The draws fed through static buffers: generator noise,
+        interpolation weights."""
         dev = real.device
         B, T = self._shapes(real)
         nz = self.gen.noise_size
@@ -530,40 +603,20 @@ class Phase3Engine(WganGpEngine):
             with K.weight_cache():
                 return self._generator_body(g["real"], g["audio"], g["slices"], g["noise_g"])
 
-        # One warm-up pass of each body on a side stream (lazy module loads and allocator growth
-        # must not happen inside a capture); it must leave no trace: the BatchNorm buffers it
-        # touches are restored, gradients are dropped, no optimizer step is taken, no host draw.
-        mods = [self.gen, self.critic]
-        saved = [[b.clone() for b in m.buffers()] for m in mods]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        # (the warm-up backward must not feed the data-parallel exchange either: no start() follows it)
-        quiet = [x.suspended() for x in (self.x_critic, self.x_gen) if x is not None]
-        with torch.cuda.stream(side), contextlib.ExitStack() as es:
-            for q in quiet:
-                es.enter_context(q)
-            critic_body()
-            gen_body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.optim_critic.zero_grad(set_to_none=True)
-        self.optim_gen.zero_grad(set_to_none=True)
-        g["keep"] = []
-        g["critic"] = torch.cuda.CUDAGraph()
-        g["critic_out"] = _capture(g["critic"], critic_body, dev, g["keep"])
-        # the gradient tensors live in this graph's private pool: a graph captured later for another
-        # shape allocates its own, so each replay re-binds p.grad to the set it writes
-        g["critic_grads"] = [p.grad for p in self.critic.parameters()]
-        g["gen"] = torch.cuda.CUDAGraph()
-        g["gen_out"] = _capture(g["gen"], gen_body, dev, g["keep"], pool=g["critic"].pool())
-        g["gen_grads"] = [p.grad for p in self.gen.parameters()]
-        with torch.no_grad():
-            for m, bufs in zip(mods, saved):
-                for b, v in zip(m.buffers(), bufs):
-                    b.copy_(v)
-        torch.cuda.synchronize(dev)
-        self._graphs[key] = g
-        return g
+        return g, [("critic", critic_body, None, self.critic), ("gen", gen_body, "critic", self.gen)]
+
+    def _feed_critic(self, g, real, audio, audio_slices):
+        B, T = self._shapes(real)
+        g["real"].copy_(real.reshape(g["real"].shape))
+        g["audio"].copy_(audio)
+        g["slices"].copy_(audio_slices)
+        # host draws in the reference's order: generator noise, then the penalty's alpha
+        g["noise_c"].copy_(to_device_async(torch.randn(B, T, self.gen.noise_size), real.device))
+        g["alpha"].copy_(to_device_async(torch.rand(B, 1), real.device))
+
+    def _feed_generator(self, g, real, audio, audio_slices):
+        B, T = self._shapes(real)
+        g["noise_g"].copy_(to_device_async(torch.randn(B, T, self.gen.noise_size), real.device))
 
     @torch.no_grad()
     def validation_l1(self, batches):
@@ -597,9 +650,15 @@ class Phase2Engine(WganGpEngine):
         self.scheduler_critic = optim.lr_scheduler.MultiStepLR(self.optim_critic, milestones=ms, gamma=0.8)
         self.scheduler_gen = optim.lr_scheduler.MultiStepLR(self.optim_gen, milestones=ms, gamma=0.8)
         self.host_noise = True  # draw noise on the host generator (matches the CPU reference)
+        self._ready0 = None     # _always_ready
         if os.environ.get("M2D_MANUAL_CRITIC", "1") != "0" and CriticStep.supports(critic):
             self.manual_critic = CriticStep(critic, self.gamma, lp=True)
             self.manual_critic.join_pairs = self._join_pairs
+
+    def _shapes(self, real):
+        B = real.size(0)
+        T = real.numel() // (B * self.output_size)
+        return B, T
 
     def _noise(self, B, T, device):
         if self.host_noise:
@@ -610,7 +669,7 @@ class Phase2Engine(WganGpEngine):
         """The generator's only input is noise the engine draws itself: its forward may always run one iteration
         ahead on the second stream (an event that has long completed plays the loader's `inputs_ready`)."""
         if self._inputs_ready is None and device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
-            if getattr(self, "_ready0", None) is None:
+            if self._ready0 is None:
                 self._ready0 = torch.cuda.current_stream(device).record_event()
             self._inputs_ready = self._ready0
 
@@ -621,8 +680,7 @@ class Phase2Engine(WganGpEngine):
 
     def _critic_body(self, real, noise, alpha):
         """noise / alpha: None = drawn where the reference draws them (phase2/train.py:139-140, losses.py:15)."""
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         self._always_ready(real.device)
         # (the noise is drawn inside the forward: on the generator's stream when it runs ahead)
         fake_rows = self._generator_forward_nograd(
@@ -633,8 +691,7 @@ class Phase2Engine(WganGpEngine):
         return self._critic_from_fake(real, fake_rows, alpha)
 
     def _critic_from_fake(self, real, fake_rows, alpha):
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         if self.manual_critic is not None:
             if alpha is None:
                 alpha = to_device_async(torch.rand(B, 1), real.device)  # host draw, as losses.py:15
@@ -652,13 +709,16 @@ class Phase2Engine(WganGpEngine):
         self._finish_critic_step()
         out = self._generator_body(real, None)
         self._gen_step()
-        self.scheduler_critic.step()
-        self.scheduler_gen.step()
+        self._step_schedulers()
         return out
 
+    def _step_schedulers(self):
+        # (phase2/train.py:179-180: on generator iterations only)
+        self.scheduler_critic.step()
+        self.scheduler_gen.step()
+
     def _generator_body(self, real, noise):
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         self.optim_gen.zero_grad(set_to_none=True)
         if noise is None:
             noise = self._noise(B, T, real.device)
@@ -672,73 +732,13 @@ class Phase2Engine(WganGpEngine):
             err_gen.backward()
         return {"loss_gen": err_gen.detach()}
 
-    # ------------------------------------------------------------------ captured-graph mode (as Phase3Engine's)
-    def enable_graphs(self, on=True):
-        """Replay each loop body's forward / backward as one captured HIP graph per batch shape. The optimizer and
-        scheduler steps and the gradient exchange stay eager; the noise and the interpolation weights are drawn
-        where the eager path draws them, in the same order, and fed through static buffers."""
-        self._use_graphs = bool(on)
-        self._graphs = {}
-        if on and hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        return self
-
-    def train_step(self, real, inputs_ready=None):
-        if not getattr(self, "_use_graphs", False) or real.device.type != "cuda":
-            return super().train_step(real, inputs_ready=inputs_ready)
-        self.total_iterations += 1
-        self._check_async()
-        self._finish_critic_step()
-        g = self._graph_for(real)
-        B, T = g["noise_c"].shape[0], g["noise_c"].shape[1]
+    # ------------------------------------------------------------------ captured-graph mode (WganGpEngine.enable_graphs)
+    def _graph_bodies(self, real):
+        """Three graphs per batch shape: the critic iteration's generator forward, the critic iteration from its
+        result, the generator iteration. The noise and the interpolation weights are drawn where the eager path draws
+        them, in the same order."""
         dev = real.device
-        # the critic iteration's generator forward is a graph of its own, replayed on the generator stream one
-        # iteration ahead (as the eager engine pipelines it): a single replay queue would put its 0.5 ms of recurrent
-        # launches in line with the critic (2.64 ms per body against 2.2 eager)
-        self._always_ready(dev)
-
-        def forward():
-            g["noise_c"].copy_(self._noise(B, T, dev))  # host draw where the eager path makes it
-            g["fwd"].replay()
-            return g["fake_out"]
-
-        out_rows = self._generator_forward_nograd(forward, (), dev)
-        pend, self._fake_pending = self._fake_pending, None
-        main = torch.cuda.current_stream(dev)
-        g["real"].copy_(real.reshape(g["real"].shape))
-        if self.draws_alpha:
-            g["alpha"].copy_(to_device_async(torch.rand(B, 1), dev))
-        if pend is not None:
-            main.wait_event(pend[1])
-        g["fake_in"].copy_(out_rows)
-        if pend is not None:
-            # the next forward may overwrite its output only after this copy
-            self._main_mark = main.record_event()
-        Phase3Engine._bind_grads(self.critic, g["critic_grads"])
-        g["critic"].replay()
-        self._begin_critic_step()
-        out = dict(g["critic_out"])
-        if self.total_iterations % self.n_critic_steps == 0:
-            self._finish_critic_step()
-            g["noise_g"].copy_(self._noise(B, T, real.device))
-            Phase3Engine._bind_grads(self.gen, g["gen_grads"])
-            g["gen"].replay()
-            self._gen_step()
-            self.scheduler_critic.step()
-            self.scheduler_gen.step()
-            out.update(g["gen_out"])
-        self.last = out
-        self.last_full.update(out)
-        return out
-
-    def _graph_for(self, real):
-        key = tuple(real.shape)
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
-        dev = real.device
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         g = {"real": torch.empty_like(real).copy_(real), "noise_c": torch.zeros(B, T, self.input_size, device=dev),
              "noise_g": torch.zeros(B, T, self.input_size, device=dev), "alpha": torch.full((B, 1), 0.5, device=dev),
              "fake_in": torch.zeros(B * T, self.output_size, device=dev)}
@@ -757,41 +757,42 @@ class Phase2Engine(WganGpEngine):
             with K.weight_cache():
                 return self._generator_body(g["real"], g["noise_g"])
 
-        mods = [self.gen, self.critic]
-        saved = [[b.clone() for b in m.buffers()] for m in mods]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        quiet = [x.suspended() for x in (self.x_critic, self.x_gen) if x is not None]
-        with torch.cuda.stream(side), contextlib.ExitStack() as es:
-            for q in quiet:
-                es.enter_context(q)
-            fwd_body()
-            critic_body()
-            gen_body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.optim_critic.zero_grad(set_to_none=True)
-        self.optim_gen.zero_grad(set_to_none=True)
         # the forward graph replays on the generator stream WHILE the critic graph of the previous body runs: it gets
         # a memory pool of its own (graphs that share a pool reuse each other's freed intermediates, which is only
         # safe when they never overlap - sharing one here let the critic overwrite the recurrent layers' outputs
         # under the running GRU kernel, which then spun on its hand-off sentinel until the timeout)
-        g["keep"] = []
-        g["fwd"] = torch.cuda.CUDAGraph()
-        g["fake_out"] = _capture(g["fwd"], fwd_body, dev, g["keep"])
-        g["critic"] = torch.cuda.CUDAGraph()
-        g["critic_out"] = _capture(g["critic"], critic_body, dev, g["keep"])
-        g["critic_grads"] = [p.grad for p in self.critic.parameters()]
-        g["gen"] = torch.cuda.CUDAGraph()
-        g["gen_out"] = _capture(g["gen"], gen_body, dev, g["keep"], pool=g["critic"].pool())
-        g["gen_grads"] = [p.grad for p in self.gen.parameters()]
-        with torch.no_grad():
-            for m, bufs in zip(mods, saved):
-                for b, v in zip(m.buffers(), bufs):
-                    b.copy_(v)
-        torch.cuda.synchronize(dev)
-        self._graphs[key] = g
-        return g
+        return g, [("fwd", fwd_body, None, None), ("critic", critic_body, None, self.critic),
+                   ("gen", gen_body, "critic", self.gen)]
+
+    def _feed_critic(self, g, real):
+        B, T = g["noise_c"].shape[0], g["noise_c"].shape[1]
+        dev = real.device
+        # the critic iteration's generator forward is a graph of its own, replayed on the generator stream one
+        # iteration ahead (as the eager engine pipelines it): a single replay queue would put its 0.5 ms of recurrent
+        # launches in line with the critic (2.64 ms per body against 2.2 eager)
+        self._always_ready(dev)
+
+        def forward():
+            g["noise_c"].copy_(self._noise(B, T, dev))  # host draw where the eager path makes it
+            g["fwd"].replay()
+            return g["fwd_out"]
+
+        out_rows = self._generator_forward_nograd(forward, (), dev)
+        pend, self._fake_pending = self._fake_pending, None
+        main = torch.cuda.current_stream(dev)
+        g["real"].copy_(real.reshape(g["real"].shape))
+        if self.draws_alpha:
+            g["alpha"].copy_(to_device_async(torch.rand(B, 1), dev))
+        if pend is not None:
+            main.wait_event(pend[1])
+        g["fake_in"].copy_(out_rows)
+        if pend is not None:
+            # the next forward may overwrite its output only after this copy
+            self._main_mark = main.record_event()
+
+    def _feed_generator(self, g, real):
+        B, T = g["noise_g"].shape[0], g["noise_g"].shape[1]
+        g["noise_g"].copy_(self._noise(B, T, real.device))
 
 
 class Phase2GanEngine(Phase2Engine):
@@ -817,8 +818,7 @@ class Phase2GanEngine(Phase2Engine):
 
     def _critic_from_fake(self, real, fake_rows, alpha=None):
         """err_critic = BCE(critic(real), 1) + BCE(critic(fake), 0) (phase2/train.py:217-219); `alpha` is not used."""
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         if self.manual_critic is not None:
             return self.manual_critic.run(real, fake_rows, on_grads=self._poll_exchange())
         fake = fake_rows.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
@@ -832,8 +832,7 @@ class Phase2GanEngine(Phase2Engine):
     def _generator_body(self, real, noise):
         """err_gen = BCE(critic(fake), 1) + eta * tv_loss(fake) (phase2/train.py:230-233), the critic frozen: the
         reference's critic gradients of this step are zeroed before anything reads them."""
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         self.optim_gen.zero_grad(set_to_none=True)
         if noise is None:
             noise = self._noise(B, T, real.device)
@@ -906,9 +905,7 @@ class Phase2CondEngine(Phase2Engine):
     def enable_graphs(self, on=True):
         if on:
             raise NotImplementedError("Phase2CondEngine: captured-graph mode is not supported for the conditional loop")
-        self._use_graphs = False
-        self._graphs = {}
-        return self
+        return super().enable_graphs(False)
 
     def train_step(self, real, real_labels, inputs_ready=None):
         return WganGpEngine.train_step(self, real, self._real_labels(real_labels, real.device), inputs_ready=inputs_ready)
@@ -919,8 +916,7 @@ class Phase2CondEngine(Phase2Engine):
         return out
 
     def _critic_body(self, real, real_labels, noise=None, alpha=None):
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         dev = real.device
         self._always_ready(dev)
         drawn = []
@@ -943,8 +939,7 @@ class Phase2CondEngine(Phase2Engine):
         return self._cond_critic(real, real_labels, fake_rows, fake_lbl, alpha)
 
     def _cond_critic(self, real, real_labels, fake_rows, fake_lbl, alpha):
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         if self.manual_critic is not None:
             return self.manual_critic.run(real, fake_rows, real_labels, fake_lbl, alpha,
                                           keep=self._critic_keep(B, T, real.device), on_grads=self._poll_exchange())
@@ -965,8 +960,7 @@ class Phase2CondEngine(Phase2Engine):
         return out
 
     def _generator_body(self, real, real_labels, noise=None):
-        B = real.size(0)
-        T = real.numel() // (B * self.output_size)
+        B, T = self._shapes(real)
         dev = real.device
         self.optim_gen.zero_grad(set_to_none=True)
         lbl = self._labels(B, dev)
@@ -1037,52 +1031,17 @@ class Phase1Engine(WganGpEngine):
             err_gen.backward()
         return {"loss_gen": err_gen.detach()}
 
-    # ------------------------------------------------------------------ captured-graph mode
-    def enable_graphs(self, on=True):
-        """Replay each loop body's forward / backward as one captured HIP graph per batch shape: the phase-1 networks
-        are a few dozen sub-10 us launches per pass, so the eager loop is bound by the host's launch rate (2.8 ms per
-        body for 0.75 ms of kernels at batch 64). Optimizer steps and the gradient exchange stay eager. Every HOST draw
-        of the body - generator noise, interpolation weights, the dropout masks of both networks (the reference never
-        calls .eval()) - is recorded on a `layers.DrawTape` and made again, in the same order on the same generator,
-        before each replay: results equal the eager path's (tests/test_critic_step.py)."""
-        self._use_graphs = bool(on)
-        self._graphs = {}
-        if on and hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        return self
-
-    def train_step(self, real, inputs_ready=None):
-        if not getattr(self, "_use_graphs", False) or real.device.type != "cuda":
-            return super().train_step(real, inputs_ready=inputs_ready)
-        self.total_iterations += 1
-        self._finish_critic_step()
-        g = self._graph_for(real)
-        g["real"].copy_(real.reshape(g["real"].shape))
-        g["tape_c"].refill()
-        Phase3Engine._bind_grads(self.critic, g["critic_grads"])
-        g["critic"].replay()
-        self._begin_critic_step()
-        out = dict(g["critic_out"])
-        if self.total_iterations % self.n_critic_steps == 0:
-            self._finish_critic_step()
-            g["tape_g"].refill()
-            Phase3Engine._bind_grads(self.gen, g["gen_grads"])
-            g["gen"].replay()
-            self._gen_step()
-            out.update(g["gen_out"])
-        self.last = out
-        self.last_full.update(out)
-        return out
-
-    def _graph_for(self, real):
-        key = tuple(real.shape)
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
-        dev = real.device
+    # ------------------------------------------------------------------ captured-graph mode (WganGpEngine.enable_graphs)
+    def _graph_bodies(self, real):
+        """The phase-1 networks are a few dozen sub-10 us launches per pass, so the eager loop is bound by the host's
+        launch rate (2.8 ms per body for 0.75 ms of kernels at batch 64). Every HOST draw of the body - generator
+        noise, interpolation weights, the dropout masks of both networks (the reference never calls .eval()) - is
+        recorded on a `layers.DrawTape` and made again, in the same order on the same generator, before each replay:
+        results equal the eager path's (tests/test_critic_step.py)."""
         g = {"real": torch.empty_like(real).copy_(real), "tape_c": DrawTape(), "tape_g": DrawTape()}
         K = kernels.impl()
 
+        # (the warm-up pass records the tapes; the static buffers hold zeros: values do not matter there)
         def critic_body():
             g["tape_c"].rewind()
             with K.weight_cache(), draw_tape(g["tape_c"]):
@@ -1093,34 +1052,14 @@ class Phase1Engine(WganGpEngine):
             with K.weight_cache(), draw_tape(g["tape_g"]):
                 return self._generator_body(g["real"])
 
-        mods = [self.gen, self.critic]
-        saved = [[b.clone() for b in m.buffers()] for m in mods]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        quiet = [x.suspended() for x in (self.x_critic, self.x_gen) if x is not None]
-        with torch.cuda.stream(side), contextlib.ExitStack() as es:
-            for q in quiet:
-                es.enter_context(q)
-            critic_body()  # (records the tapes; the static buffers hold zeros: values do not matter here)
-            gen_body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.optim_critic.zero_grad(set_to_none=True)
-        self.optim_gen.zero_grad(set_to_none=True)
-        g["keep"] = []
-        g["critic"] = torch.cuda.CUDAGraph()
-        g["critic_out"] = _capture(g["critic"], critic_body, dev, g["keep"])
-        g["critic_grads"] = [p.grad for p in self.critic.parameters()]
-        g["gen"] = torch.cuda.CUDAGraph()
-        g["gen_out"] = _capture(g["gen"], gen_body, dev, g["keep"], pool=g["critic"].pool())
-        g["gen_grads"] = [p.grad for p in self.gen.parameters()]
-        with torch.no_grad():
-            for m, bufs in zip(mods, saved):
-                for b, v in zip(m.buffers(), bufs):
-                    b.copy_(v)
-        torch.cuda.synchronize(dev)
-        self._graphs[key] = g
-        return g
+        return g, [("critic", critic_body, None, self.critic), ("gen", gen_body, "critic", self.gen)]
+
+    def _feed_critic(self, g, real):
+        g["real"].copy_(real.reshape(g["real"].shape))
+        g["tape_c"].refill()
+
+    def _feed_generator(self, g, real):
+        g["tape_g"].refill()
 
 
 # =========================================================================================== synthetic data
