@@ -24,7 +24,8 @@ class AdamItem(_c.Structure):
                 ("cout", _I), ("cin", _I), ("ks", _I), ("reserved", _I)]
 
 
-# name -> (restype, argtypes); mirrors include/m2d.h line by line
+# name -> (restype, argtypes); mirrors include/m2d.h declaration by declaration, in the header's order (a new entry
+# point goes where its declaration stands)
 SIGNATURES = {
     "m2d_last_error": (_c.c_char_p, []),
     "m2d_version": (_I, []),
@@ -36,7 +37,6 @@ SIGNATURES = {
     "m2d_plan_model_get": (_I, []),
     "m2d_conv1d_fwd": (_I, [_F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _f, _F, _F, _f, _F, _F, _S, _F]),
     "m2d_conv1d_bwd_data": (_I, [_F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _F, _f, _F, _f, _F, _S, _F]),
-    "m2d_conv1d_pack_weights": (_I, [_F, _F, _F, _I, _I, _I, _F]),
     "m2d_conv1d_bwd_weight": (_I, [_F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _F, _f, _F, _S, _F]),
     "m2d_conv1d_fwd_sum": (_I, [_F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _f, _F, _F, _f, _F, _S, _F]),
     "m2d_conv1d_k4_applicable": (_I, [_I, _I, _I, _I, _I, _I]),
@@ -44,13 +44,9 @@ SIGNATURES = {
     "m2d_conv1d_pack_weights_k4": (_I, [_F, _F, _I, _I, _I, _I, _F]),
     "m2d_conv1d_fwd_k4": (_I, [_F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _f, _F, _F, _f, _F, _F, _S, _F]),
     "m2d_conv1d_bwd_data_res": (_I, [_F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _F, _f, _F, _F, _f, _F, _S, _F]),
-    "m2d_bn_update_running": (_I, [_F, _c.c_double, _F, _F, _F, _I, _f, _f, _F]),
-    "m2d_bn_fwd_sums_pool_to": (_I, [_F, _F, _c.c_double, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _f, _f, _I, _f,
-                                    _c.c_longlong, _F]),
-    "m2d_bn_fwd_sums_upsample2_to": (_I, [_F, _F, _c.c_double, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _f, _f, _I, _f,
-                                         _c.c_longlong, _F]),
-    "m2d_conv1d_bwd_data_shared_mask": (_I, [_F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _F, _f, _I, _F, _S, _F]),
     "m2d_conv1d_bwd_weight_from": (_I, [_F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _F, _f, _I, _F, _S, _F]),
+    "m2d_bn_update_running": (_I, [_F, _c.c_double, _F, _F, _F, _I, _f, _f, _F]),
+    "m2d_conv1d_bwd_data_shared_mask": (_I, [_F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _F, _f, _I, _F, _S, _F]),
     "m2d_gemm_ld": (_I, [_I, _F, _I, _F, _I, _F, _F, _I, _I, _I, _I, _I, _f, _F, _f, _F, _f, _F, _S, _F]),
     "m2d_tanh_fwd": (_I, [_F, _F, _S, _F]),
     "m2d_tanh_bwd": (_I, [_F, _F, _F, _S, _F]),
@@ -59,12 +55,13 @@ SIGNATURES = {
     "m2d_wgan_critic_loss": (_I, [_F, _I, _F, _F, _f, _F, _F]),
     "m2d_conv1d_fwd_windows": (_I, [_F, _I, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _I, _f, _F, _F, _S, _F]),
     "m2d_conv1d_bwd_weight_windows": (_I, [_F, _I, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _F, _f, _F, _S, _F]),
+    "m2d_conv1d_pack_weights": (_I, [_F, _F, _F, _I, _I, _I, _F]),
     "m2d_conv1d_workspace_bytes": (_S, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "m2d_gemm": (_I, [_I, _F, _F, _F, _F, _I, _I, _I, _I, _f, _F, _f, _F, _f, _F, _S, _F]),
     "m2d_gemm_workspace_bytes": (_S, [_I, _I, _I, _I]),
-    "m2d_bn_workspace_bytes": (_S, [_I]),
     "m2d_stream_scratch_set": (_I, [_F, _F, _S]),
-    "m2d_stream_create": (_I, [ctypes.POINTER(ctypes.c_void_p)]),
+    "m2d_stream_create": (_I, [_c.POINTER(_c.c_void_p)]),
+    "m2d_bn_workspace_bytes": (_S, [_I]),
     "m2d_bn_scratch_bytes": (_S, [_I]),
     "m2d_bn_fwd": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _f, _f, _I, _I, _f, _F, _F, _S, _F, _F]),
     "m2d_bn_bwd": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _f, _F, _S, _F, _F]),
@@ -73,6 +70,10 @@ SIGNATURES = {
     "m2d_bn_fwd_to": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _f, _f, _I, _I, _f, _F, _F, _S, _F, _c.c_longlong, _F]),
     "m2d_bn_fwd_sums_to": (_I, [_F, _F, _c.c_double, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _f, _f, _I, _f, _F,
                                 _c.c_longlong, _F]),
+    "m2d_bn_fwd_sums_pool_to": (_I, [_F, _F, _c.c_double, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _f, _f, _I, _f,
+                                    _c.c_longlong, _F]),
+    "m2d_bn_fwd_sums_upsample2_to": (_I, [_F, _F, _c.c_double, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _f, _f, _I, _f,
+                                         _c.c_longlong, _F]),
     "m2d_bn_bwd_stats": (_I, [_F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _f, _F, _F]),
     "m2d_bn_bwd_sums": (_I, [_F, _F, _F, _F, _F, _F, _F, _F, _c.c_double, _F, _F, _F, _I, _I, _I, _I, _f, _F, _S, _F]),
     "m2d_channel_sums": (_I, [_F, _F, _f, _F, _I, _I, _I, _F, _S, _F, _F]),
@@ -94,12 +95,6 @@ SIGNATURES = {
     "m2d_cross_entropy_bwd": (_I, [_F, _F, _F, _F, _I, _I, _F]),
     "m2d_bce_logits_fwd": (_I, [_F, _I, _f, _I, _f, _F, _F, _F]),
     "m2d_bce_logits_bwd": (_I, [_F, _I, _f, _I, _f, _F, _F, _F]),
-    "m2d_label_concat": (_I, [_F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _F]),
-    "m2d_pose_pack3_label": (_I, [_F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _F]),
-    "m2d_label_embed_bwd": (_I, [_F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _F]),
-    "m2d_dropout": (_I, [_F, _F, _F, _c.c_longlong, _f, _f, _c.c_ulonglong, _c.c_ulonglong, _I, _F]),
-    "m2d_randn_frames": (_I, [_F, _c.c_ulonglong, _c.c_longlong, _I, _I, _I, _F]),
-    "m2d_render_sticks": (_I, [_F, _L, _I, _I, _F, _F]),
     "m2d_gp_interpolate": (_I, [_F, _F, _F, _F, _I, _I, _F]),
     "m2d_gp_penalty_workspace_bytes": (_S, [_I]),
     "m2d_gp_penalty_fwd": (_I, [_F, _F, _F, _I, _I, _I, _F, _S, _F]),
@@ -118,6 +113,12 @@ SIGNATURES = {
     "m2d_upsample2_fwd_to": (_I, [_F, _F, _S, _I, _I, _c.c_longlong, _F]),
     "m2d_maxpool2_fwd_from": (_I, [_F, _F, _S, _I, _I, _c.c_longlong, _F]),
     "m2d_upsample2_bwd": (_I, [_F, _F, _S, _I, _F]),
+    "m2d_label_concat": (_I, [_F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _F]),
+    "m2d_pose_pack3_label": (_I, [_F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _F]),
+    "m2d_label_embed_bwd": (_I, [_F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _F]),
+    "m2d_dropout": (_I, [_F, _F, _F, _c.c_longlong, _f, _f, _c.c_ulonglong, _c.c_ulonglong, _I, _F]),
+    "m2d_randn_frames": (_I, [_F, _c.c_ulonglong, _c.c_longlong, _I, _I, _I, _F]),
+    "m2d_render_sticks": (_I, [_F, _L, _I, _I, _F, _F]),
 }
 
 _lib = None
@@ -147,14 +148,6 @@ def lib():
         fn.argtypes = args
     _lib = h
     return _lib
-
-
-def install_backend(handle):
-    """Test hook: replace the library handle (tests/fake_backend.py). Never used by the product."""
-    global _lib
-    prev = _lib
-    _lib = handle
-    return prev
 
 
 def check(rc, what):

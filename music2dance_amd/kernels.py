@@ -4,6 +4,9 @@ PyTorch is plumbing here: it owns device memory (outputs and scratch come from t
 caching allocator, so the calls are hipGraph-capture safe) and the current HIP stream.
 Every method enqueues hand-written gfx950 kernels and nothing else; inputs must be
 contiguous fp32 tensors on a HIP device, otherwise the call raises (no fallback).
+
+A method checks its arguments, allocates outputs (and `_workspace`), and hands pointers and sizes to `_launch` under
+the entry point's name; the weight images the GEMMs read are kept by `HipKernels._image`.
 """
 import contextlib
 import ctypes
@@ -52,6 +55,19 @@ def _chk_track(track, dev, T, hop, window):
     return B, S
 
 
+def _chk_labels(labels, dev, n, what):
+    """class indices handed to a kernel: a contiguous int64 tensor of n entries on the kernels' device"""
+    if not labels.is_cuda or labels.device != dev or labels.dtype != torch.int64 or not labels.is_contiguous():
+        raise _lib.M2dError("%s: labels must be a contiguous int64 tensor on %s" % (what, dev))
+    if labels.numel() != n:
+        raise _lib.M2dError("%s: %d labels for %d rows" % (what, labels.numel(), n))
+
+
+def _bcl(x):
+    """(B, C, L) of an activation shaped (B, C, L) or (B, C)"""
+    return x.shape[0], x.shape[1], x.shape[2] if x.dim() == 3 else 1
+
+
 _STREAM_SCRATCH = {}
 _FUSED_SPLITK = os.environ.get("M2D_FUSED_SPLITK", "1") != "0"
 _TICKET_WORDS = 16384   # 4 bytes per output tile of a split-K launch (include/m2d.h: 64 KB covers every shape)
@@ -60,6 +76,12 @@ _BN_MAX_C = 4096        # widest channel / feature count a reducing call may hav
 
 def _capturing():
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def _register_tickets(raw, t):
+    """Tell the library which zero-kept ticket scratch raw stream `raw` has (None: none, two-launch split-K)."""
+    rc = _lib.lib().m2d_stream_scratch_set(raw, _ptr(t), 0 if t is None else t.numel() * 4)
+    _lib.check(rc, "m2d_stream_scratch_set")
 
 
 def _stream(dev):
@@ -75,7 +97,7 @@ def _stream(dev):
         # two-launch split-K, which needs no state.
         t = torch.zeros(_TICKET_WORDS, dtype=torch.int32, device=dev)
         _STREAM_SCRATCH[(idx, s)] = t
-        _lib.check(_lib.lib().m2d_stream_scratch_set(s, t.data_ptr(), t.numel() * 4), "m2d_stream_scratch_set")
+        _register_tickets(s, t)
     return s
 
 
@@ -97,6 +119,18 @@ def _on(dev):
     return torch.cuda.device(dev)
 
 
+def _launch(name, dev, *args):
+    """THE launch: entry point `name` of the library with `args` and, behind them, the raw current stream of `dev`
+    (every launching entry point takes its stream last), under the device guard; a non-zero return raises, naming
+    `name`. Callers pass device pointers (`_ptr`) and plain numbers. The stream is looked up here, i.e. after the
+    caller has allocated its outputs and workspace: the first look-up on a stream creates its ticket scratch, and
+    `private_scratch.adopt` runs from it."""
+    with _on(dev):
+        rc = getattr(_lib.lib(), name)(*args, _stream(dev))
+    if rc != 0:  # (tested here: this is on the host path of every launch, and the check is one more call)
+        _lib.check(rc, name)
+
+
 _WS_BYTES = {}
 
 
@@ -111,10 +145,13 @@ def _ws_bytes(name, *args):
     return n
 
 
-def _ws(nbytes, dev):
+def _workspace(dev, query, *shape):
+    """The workspace the library's size query `query` asks for at `shape` -> (tensor or None, its size in bytes)."""
+    nbytes = _ws_bytes(query, *shape)
     if nbytes <= 0:
-        return None
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+        return None, 0
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+    return ws, ws.numel() * 4
 
 
 _BN_SCRATCH = {}
@@ -157,11 +194,15 @@ class private_scratch:
         self.saved = {}
 
     @staticmethod
-    def _register(raw, t):
-        if t is None:
-            _lib.check(_lib.lib().m2d_stream_scratch_set(raw, None, 0), "m2d_stream_scratch_set")
-        else:
-            _lib.check(_lib.lib().m2d_stream_scratch_set(raw, t.data_ptr(), t.numel() * 4), "m2d_stream_scratch_set")
+    def _install(key, tickets, sums):
+        """Make (tickets, sums) the scratch of stream `key` in the module's tables and in the library (None: none)."""
+        for table, t in ((_STREAM_SCRATCH, tickets), (_BN_SCRATCH, sums)):
+            if t is None:
+                table.pop(key, None)
+            else:
+                table[key] = t
+        if _FUSED_SPLITK:
+            _register_tickets(key[1], tickets)
 
     def adopt(self, key):
         """First launch on stream `key` = (device index, raw stream) inside the scope: give it one of the sets."""
@@ -170,13 +211,7 @@ class private_scratch:
         pair = self.free.pop() if self.free else (None, None)
         self.by_stream[key] = pair
         self.saved[key] = (_STREAM_SCRATCH.get(key), _BN_SCRATCH.get(key))
-        for table, t in ((_STREAM_SCRATCH, pair[0]), (_BN_SCRATCH, pair[1])):
-            if t is None:
-                table.pop(key, None)
-            else:
-                table[key] = t
-        if _FUSED_SPLITK:
-            self._register(key[1], pair[0])
+        self._install(key, *pair)
 
     def __enter__(self):
         global _PRIVATE
@@ -186,14 +221,8 @@ class private_scratch:
     def __exit__(self, *exc):
         global _PRIVATE
         _PRIVATE = self._outer
-        for key, (old_t, old_b) in self.saved.items():
-            for table, t in ((_STREAM_SCRATCH, old_t), (_BN_SCRATCH, old_b)):
-                if t is None:
-                    table.pop(key, None)
-                else:
-                    table[key] = t
-            if _FUSED_SPLITK:
-                self._register(key[1], old_t)
+        for key, old in self.saved.items():
+            self._install(key, *old)
         self.saved = {}
         return False
 
@@ -225,18 +254,35 @@ def conv_out_len(L, ks, stride, pad):
     return (L + 2 * pad - ks) // stride + 1
 
 
+def _gemm_shape(mode, a, b):
+    """mode 0: a(M,K) b(N,K)^T; 1: a(M,K) b(K,N); 2: a(K,M)^T b(K,N) -> (M, N, K)"""
+    if mode == 0:
+        M, K = a.shape
+        N, K2 = b.shape
+    elif mode == 1:
+        M, K = a.shape
+        K2, N = b.shape
+    else:
+        K, M = a.shape
+        K2, N = b.shape
+    assert K == K2, "gemm: inner dimension mismatch"
+    return M, N, K
+
+
 class HipKernels:
     """The product implementation: every method is one or a few HIP kernel launches."""
 
     name = "hip"
 
-    # ---------------------------------------------------------------- conv1d
+    # ---------------------------------------------------------------- weight images
     def __init__(self):
-        # packed weight images (include/m2d.h: m2d_conv1d_pack_weights) of live weight tensors; only
-        # kept inside a weight_cache() scope, i.e. while the caller guarantees the weights are constant
+        # images of live weight tensors (packed conv weights, include/m2d.h: m2d_conv1d_pack_weights; W^T of the GRUs):
+        # (id(w), kind) -> (weakref to w, w._version, raw stream or None, image). Only kept inside a weight_cache()
+        # scope, i.e. while the caller guarantees the weights are constant
         self._packed = {}
         self._cache_depth = 0
         self.pack_launches = 0
+        self._adam_kept = set()   # keys of the images adam_multi has rewritten since the last invalidate_packed()
 
     @contextlib.contextmanager
     def weight_cache(self, keep=False):
@@ -258,44 +304,68 @@ class HipKernels:
                 self._packed.clear()
 
     def invalidate_packed(self, tensors=None):
-        """Drop the packed images of `tensors` (the parameters an optimizer step just changed), or all of them."""
+        """Drop the images of `tensors` (the parameters an optimizer step just changed), or all of them."""
         if tensors is None:
             self._packed.clear()
         else:
-            kept = getattr(self, "_adam_kept", ())   # (w_fwd, w_bwd) images adam_multi has just rewritten stay
-            for w in tensors:
-                if id(w) not in kept:
-                    self._packed.pop(id(w), None)
-                self._packed.pop((id(w), "T"), None)
-                for key in [k for k in self._packed if isinstance(k, tuple) and k[0] == id(w)]:
-                    self._packed.pop(key, None)
+            ids = {id(w) for w in tensors}
+            # the (w_fwd, w_bwd) images adam_multi has just rewritten stay
+            for key in [k for k in self._packed if k[0] in ids and k not in self._adam_kept]:
+                del self._packed[key]
             self._adam_kept = set()
 
-    def packed_weights(self, w):
-        """(w_fwd (Cin, ks, Cout), w_bwd (Cout, ks, Cin)): the K-major images of a conv weight the forward / backward-data
-        GEMMs read (written on the current stream)."""
+    def _image(self, w, kind, build):
+        """The image `build()` makes of weight tensor `w` on the current stream, one per (tensor, kind). Inside a
+        weight_cache() scope it is kept and handed out again while it is of this very tensor (not another one at
+        the same address), the tensor's version counter has not moved, and the asking stream is the one it was
+        written on (or it is marked valid on every stream: None, see adam_multi); it goes when the tensor dies."""
         stream = _stream(w.device)
-        key = id(w)
+        key = (id(w), kind)
         if self._cache_depth > 0:
             ent = self._packed.get(key)
             if ent is not None and ent[0]() is w and ent[1] == w._version and (ent[2] is None or ent[2] == stream):
-                return ent[3], ent[4]
-        Cout, Cin, ks = w.shape
-        wf = torch.empty((Cin, ks, Cout), dtype=torch.float32, device=w.device)
-        wb = torch.empty((Cout, ks, Cin), dtype=torch.float32, device=w.device)
-        with _on(w.device):
-            rc = _lib.lib().m2d_conv1d_pack_weights(_ptr(w), _ptr(wf), _ptr(wb), Cout, Cin, ks, stream)
-        _lib.check(rc, "m2d_conv1d_pack_weights")
-        self.pack_launches += 1
+                return ent[3]
+        image = build()
         if self._cache_depth > 0:
             packed = self._packed
 
             def _drop(_ref, key=key):
                 packed.pop(key, None)
 
-            packed[key] = (weakref.ref(w, _drop), w._version, stream, wf, wb)
-        return wf, wb
+            packed[key] = (weakref.ref(w, _drop), w._version, stream, image)
+        return image
 
+    def packed_weights(self, w):
+        """(w_fwd (Cin, ks, Cout), w_bwd (Cout, ks, Cin)): the K-major images of a conv weight the forward / backward-data
+        GEMMs read (written on the current stream)."""
+        def build():
+            Cout, Cin, ks = w.shape
+            wf = torch.empty((Cin, ks, Cout), dtype=torch.float32, device=w.device)
+            wb = torch.empty((Cout, ks, Cin), dtype=torch.float32, device=w.device)
+            _launch("m2d_conv1d_pack_weights", w.device, _ptr(w), _ptr(wf), _ptr(wb), Cout, Cin, ks)
+            self.pack_launches += 1
+            return wf, wb
+
+        return self._image(w, "conv", build)
+
+    def packed_k4(self, w, pad):
+        """Wk4[(ci, tap group)][Cout][4]: the image the tap-vectorised stride-4 forward reads (cached like the others)."""
+        def build():
+            Cout, Cin, ks = w.shape
+            elems = _lib.lib().m2d_conv1d_k4_packed_elems(Cout, Cin, ks, pad)
+            out = torch.empty((elems,), dtype=torch.float32, device=w.device)
+            _launch("m2d_conv1d_pack_weights_k4", w.device, _ptr(w), _ptr(out), Cout, Cin, ks, pad)
+            self.pack_launches += 1
+            return out
+
+        return self._image(w, ("k4", pad), build)
+
+    def transposed(self, w):
+        """w.t().contiguous() of a 2-D weight (the GRU kernels read W^T), kept like the packed conv images: built
+        once per weight tensor inside a weight_cache() scope, dropped by invalidate_packed()."""
+        return self._image(w, "T", lambda: w.t().contiguous())
+
+    # ---------------------------------------------------------------- conv1d
     _SEPARATE_BIAS = os.environ.get("M2D_SEPARATE_BIAS", "1") != "0"
     _K4 = os.environ.get("M2D_K4", "1") != "0"  # A/B lever: 0 = stride-4 forwards through the generic engine
     _K4_OK = {}
@@ -308,30 +378,6 @@ class HipKernels:
         if ok is None:
             ok = self._K4_OK[key] = bool(_lib.lib().m2d_conv1d_k4_applicable(Cin, L, Cout, ks, stride, pad))
         return ok
-
-    def packed_k4(self, w, pad):
-        """Wk4[(ci, tap group)][Cout][4]: the image the tap-vectorised stride-4 forward reads (cached like the others)."""
-        stream = _stream(w.device)
-        key = (id(w), "k4", pad)
-        if self._cache_depth > 0:
-            ent = self._packed.get(key)
-            if ent is not None and ent[0]() is w and ent[1] == w._version and ent[2] == stream:
-                return ent[3]
-        Cout, Cin, ks = w.shape
-        h = _lib.lib()
-        out = torch.empty((h.m2d_conv1d_k4_packed_elems(Cout, Cin, ks, pad),), dtype=torch.float32, device=w.device)
-        with _on(w.device):
-            rc = h.m2d_conv1d_pack_weights_k4(_ptr(w), _ptr(out), Cout, Cin, ks, pad, stream)
-        _lib.check(rc, "m2d_conv1d_pack_weights_k4")
-        self.pack_launches += 1
-        if self._cache_depth > 0:
-            packed = self._packed
-
-            def _drop(_ref, key=key):
-                packed.pop(key, None)
-
-            packed[key] = (weakref.ref(w, _drop), w._version, stream, out)
-        return out
 
     @staticmethod
     def _thin(Cin, ks, stride):
@@ -351,39 +397,29 @@ class HipKernels:
         Lout = conv_out_len(L, ks, stride, pad)
         y = torch.empty((B, Cout, Lout), dtype=torch.float32, device=dev) if out is None else out
         assert tuple(y.shape) == (B, Cout, Lout)
-        h = _lib.lib()
         full_length = Lout == 1 and pad == 0 and L == ks
         if sum_out is not None:
             assert not with_stats and residual is not None and tuple(sum_out.shape) == tuple(y.shape)
-        if self._k4(Cin, L, Cout, ks, stride, pad):
-            # tap-vectorised stride-4 forward (audio critic l2..l5 and the penalty's tangent through them)
+        # tap-vectorised stride-4 forward (audio critic l2..l5 and the penalty's tangent through them), or the engine
+        k4 = self._k4(Cin, L, Cout, ks, stride, pad)
+        if k4:
             wk4 = self.packed_k4(w, pad)
-            ws = _ws(_ws_bytes('m2d_conv1d_workspace_bytes', 0, B, Cin, L, Cout, ks, stride, pad), dev)
-            sums = torch.empty((2 * Cout,), dtype=torch.float64, device=dev) if with_stats else None
-            with _on(dev):
-                rc = h.m2d_conv1d_fwd_k4(_ptr(x), _ptr(wk4), _ptr(bias), _ptr(y), _ptr(sum_out), B, Cin, L, Cout, ks,
-                                         stride, pad, act, slope, _ptr(residual), _ptr(out_mask), out_mask_slope,
-                                         _ptr(sums), _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream(dev))
-            _lib.check(rc, "m2d_conv1d_fwd_k4")
-            if sum_out is not None:
-                return y, sum_out
-            return (y, sums) if with_stats else y
-        wp = self.packed_weights(w)[0] if (Cin >= 16 and not full_length) else None
-        ws = _ws(_ws_bytes('m2d_conv1d_workspace_bytes', 0, B, Cin, L, Cout, ks, stride, pad), dev)
-        nws = 0 if ws is None else ws.numel() * 4
-        if sum_out is not None:
-            with _on(dev):
-                rc = h.m2d_conv1d_fwd_sum(_ptr(x), _ptr(w), _ptr(wp), _ptr(bias), _ptr(y), _ptr(sum_out), B, Cin, L,
-                                          Cout, ks, stride, pad, act, slope, _ptr(residual), _ptr(out_mask),
-                                          out_mask_slope, _ptr(ws), nws, _stream(dev))
-            _lib.check(rc, "m2d_conv1d_fwd_sum")
-            return y, sum_out
+        else:
+            wp = self.packed_weights(w)[0] if (Cin >= 16 and not full_length) else None
+        ws, nws = _workspace(dev, 'm2d_conv1d_workspace_bytes', 0, B, Cin, L, Cout, ks, stride, pad)
         sums = torch.empty((2 * Cout,), dtype=torch.float64, device=dev) if with_stats else None
-        with _on(dev):
-            rc = h.m2d_conv1d_fwd(_ptr(x), _ptr(w), _ptr(wp), _ptr(bias), _ptr(y), B, Cin, L, Cout, ks, stride, pad,
-                                  act, slope, _ptr(residual), _ptr(out_mask), out_mask_slope, _ptr(sums), _ptr(ws),
-                                  nws, _stream(dev))
-        _lib.check(rc, "m2d_conv1d_fwd")
+        if k4:
+            _launch("m2d_conv1d_fwd_k4", dev, _ptr(x), _ptr(wk4), _ptr(bias), _ptr(y), _ptr(sum_out), B, Cin, L, Cout,
+                    ks, stride, pad, act, slope, _ptr(residual), _ptr(out_mask), out_mask_slope, _ptr(sums), _ptr(ws),
+                    nws)
+        elif sum_out is not None:
+            _launch("m2d_conv1d_fwd_sum", dev, _ptr(x), _ptr(w), _ptr(wp), _ptr(bias), _ptr(y), _ptr(sum_out), B, Cin,
+                    L, Cout, ks, stride, pad, act, slope, _ptr(residual), _ptr(out_mask), out_mask_slope, _ptr(ws), nws)
+        else:
+            _launch("m2d_conv1d_fwd", dev, _ptr(x), _ptr(w), _ptr(wp), _ptr(bias), _ptr(y), B, Cin, L, Cout, ks,
+                    stride, pad, act, slope, _ptr(residual), _ptr(out_mask), out_mask_slope, _ptr(sums), _ptr(ws), nws)
+        if sum_out is not None:
+            return y, sum_out
         return (y, sums) if with_stats else y
 
     def conv1d_bwd_data(self, dy, w, L, stride, pad, dy_mask=None, dy_mask_slope=0.0, out_mask=None,
@@ -397,35 +433,27 @@ class HipKernels:
         assert Cout == Cout2 and Lout == conv_out_len(L, ks, stride, pad)
         dx = torch.empty((B, Cin, L), dtype=torch.float32, device=dev) if out is None else out
         assert tuple(dx.shape) == (B, Cin, L)
-        if out_mask is not None and out_mask.shape[0] != B:
+        shared_mask = out_mask is not None and out_mask.shape[0] != B
+        if shared_mask:
             mb = out_mask.shape[0]
             assert tuple(out_mask.shape[1:]) == (Cin, L) and 2 * mb >= B and dy_mask is None and residual is None
             wp = self.packed_weights(w)[1]
-            ws = _ws(_ws_bytes('m2d_conv1d_workspace_bytes', 1, B, Cin, L, Cout, ks, stride, pad), dev)
-            with _on(dev):
-                rc = _lib.lib().m2d_conv1d_bwd_data_shared_mask(_ptr(dy), _ptr(w), _ptr(wp), _ptr(dx), B, Cin, L, Cout, ks,
-                                                                stride, pad, _ptr(out_mask), out_mask_slope, mb, _ptr(ws),
-                                                                0 if ws is None else ws.numel() * 4, _stream(dev))
-            _lib.check(rc, "m2d_conv1d_bwd_data_shared_mask")
-            return dx
-        h = _lib.lib()
-        full_length = Lout == 1 and pad == 0 and L == ks
-        if (out_mask is not None or residual is not None) and self._thin(Cin, ks, stride):
-            raise _lib.M2dError("conv1d_bwd_data: out_mask / residual are not supported on the thin (Cin = 1, k25 s4) path")
-        wp = None if (full_length or self._thin(Cin, ks, stride)) else self.packed_weights(w)[1]
-        ws = _ws(_ws_bytes('m2d_conv1d_workspace_bytes', 1, B, Cin, L, Cout, ks, stride, pad), dev)
-        nws = 0 if ws is None else ws.numel() * 4
-        with _on(dev):
-            if residual is not None:
-                assert tuple(residual.shape) == tuple(dx.shape)
-                rc = h.m2d_conv1d_bwd_data_res(_ptr(dy), _ptr(w), _ptr(wp), _ptr(dx), B, Cin, L, Cout, ks, stride, pad,
-                                               _ptr(dy_mask), dy_mask_slope, _ptr(residual), _ptr(out_mask),
-                                               out_mask_slope, _ptr(ws), nws, _stream(dev))
-            else:
-                rc = h.m2d_conv1d_bwd_data(_ptr(dy), _ptr(w), _ptr(wp), _ptr(dx), B, Cin, L, Cout, ks, stride, pad,
-                                           _ptr(dy_mask), dy_mask_slope, _ptr(out_mask), out_mask_slope, _ptr(ws),
-                                           nws, _stream(dev))
-        _lib.check(rc, "m2d_conv1d_bwd_data")
+        else:
+            full_length = Lout == 1 and pad == 0 and L == ks
+            if (out_mask is not None or residual is not None) and self._thin(Cin, ks, stride):
+                raise _lib.M2dError("conv1d_bwd_data: out_mask / residual are not supported on the thin (Cin = 1, k25 s4) path")
+            wp = None if (full_length or self._thin(Cin, ks, stride)) else self.packed_weights(w)[1]
+        ws, nws = _workspace(dev, 'm2d_conv1d_workspace_bytes', 1, B, Cin, L, Cout, ks, stride, pad)
+        if shared_mask:
+            _launch("m2d_conv1d_bwd_data_shared_mask", dev, _ptr(dy), _ptr(w), _ptr(wp), _ptr(dx), B, Cin, L, Cout, ks,
+                    stride, pad, _ptr(out_mask), out_mask_slope, mb, _ptr(ws), nws)
+        elif residual is not None:
+            assert tuple(residual.shape) == tuple(dx.shape)
+            _launch("m2d_conv1d_bwd_data_res", dev, _ptr(dy), _ptr(w), _ptr(wp), _ptr(dx), B, Cin, L, Cout, ks, stride,
+                    pad, _ptr(dy_mask), dy_mask_slope, _ptr(residual), _ptr(out_mask), out_mask_slope, _ptr(ws), nws)
+        else:
+            _launch("m2d_conv1d_bwd_data", dev, _ptr(dy), _ptr(w), _ptr(wp), _ptr(dx), B, Cin, L, Cout, ks, stride,
+                    pad, _ptr(dy_mask), dy_mask_slope, _ptr(out_mask), out_mask_slope, _ptr(ws), nws)
         return dx
 
     def conv1d_bwd_weight(self, x, dy, ks, stride, pad, dy_mask=None, dy_mask_slope=0.0, with_bias=False,
@@ -451,18 +479,13 @@ class HipKernels:
                     (Lout < 16 or Cin * ks <= 512 or (Cin * ks <= 1024 and B * Lout >= 200000))
                     and not self._thin(Cin, ks, stride) and _bn_scratch(dev, Cout) is not None)
         db = torch.empty((Cout,), dtype=torch.float32, device=dev) if (with_bias and not sep_bias) else None
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_conv1d_workspace_bytes', 2, B, Cin, L, Cout, ks, stride, pad), dev)
-        nws = 0 if ws is None else ws.numel() * 4
-        with _on(dev):
-            if bias_from_sample:
-                rc = h.m2d_conv1d_bwd_weight_from(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B, Cin, L, Cout, ks, stride,
-                                                  pad, _ptr(dy_mask), dy_mask_slope, int(bias_from_sample), _ptr(ws),
-                                                  nws, _stream(dev))
-            else:
-                rc = h.m2d_conv1d_bwd_weight(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B, Cin, L, Cout, ks, stride, pad,
-                                             _ptr(dy_mask), dy_mask_slope, _ptr(ws), nws, _stream(dev))
-        _lib.check(rc, "m2d_conv1d_bwd_weight")
+        ws, nws = _workspace(dev, 'm2d_conv1d_workspace_bytes', 2, B, Cin, L, Cout, ks, stride, pad)
+        if bias_from_sample:
+            _launch("m2d_conv1d_bwd_weight_from", dev, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B, Cin, L, Cout, ks,
+                    stride, pad, _ptr(dy_mask), dy_mask_slope, int(bias_from_sample), _ptr(ws), nws)
+        else:
+            _launch("m2d_conv1d_bwd_weight", dev, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B, Cin, L, Cout, ks, stride,
+                    pad, _ptr(dy_mask), dy_mask_slope, _ptr(ws), nws)
         if sep_bias:
             f = int(bias_from_sample)
             db = self.channel_sums(dy[f:] if f else dy, None if dy_mask is None else (dy_mask[f:] if f else dy_mask), dy_mask_slope)
@@ -478,14 +501,10 @@ class HipKernels:
         assert Cin == 1, "window views are single-channel"
         Lout = conv_out_len(window, ks, stride, pad)
         y = torch.empty((B * T, Cout, Lout), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_conv1d_workspace_bytes', 0, B * T, 1, window, Cout, ks, stride, pad), dev)
+        ws, nws = _workspace(dev, 'm2d_conv1d_workspace_bytes', 0, B * T, 1, window, Cout, ks, stride, pad)
         sums = torch.empty((2 * Cout,), dtype=torch.float64, device=dev) if with_stats else None
-        with _on(dev):
-            rc = h.m2d_conv1d_fwd_windows(_ptr(track), B, S, T, hop, window, _ptr(w), _ptr(bias), _ptr(y), Cout, ks,
-                                          stride, pad, act, slope, _ptr(sums), _ptr(ws),
-                                          0 if ws is None else ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_conv1d_fwd_windows")
+        _launch("m2d_conv1d_fwd_windows", dev, _ptr(track), B, S, T, hop, window, _ptr(w), _ptr(bias), _ptr(y), Cout,
+                ks, stride, pad, act, slope, _ptr(sums), _ptr(ws), nws)
         return (y, sums) if with_stats else y
 
     def conv1d_bwd_weight_windows(self, track, T, hop, window, dy, ks, stride, pad, dy_mask=None, dy_mask_slope=0.0,
@@ -496,13 +515,9 @@ class HipKernels:
         assert N == B * T and Lout == conv_out_len(window, ks, stride, pad)
         dw = torch.empty((Cout, 1, ks), dtype=torch.float32, device=dev)
         db = torch.empty((Cout,), dtype=torch.float32, device=dev) if with_bias else None
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_conv1d_workspace_bytes', 2, B * T, 1, window, Cout, ks, stride, pad), dev)
-        with _on(dev):
-            rc = h.m2d_conv1d_bwd_weight_windows(_ptr(track), B, S, T, hop, window, _ptr(dy), _ptr(dw), _ptr(db), Cout,
-                                                 ks, stride, pad, _ptr(dy_mask), dy_mask_slope, _ptr(ws),
-                                                 0 if ws is None else ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_conv1d_bwd_weight_windows")
+        ws, nws = _workspace(dev, 'm2d_conv1d_workspace_bytes', 2, B * T, 1, window, Cout, ks, stride, pad)
+        _launch("m2d_conv1d_bwd_weight_windows", dev, _ptr(track), B, S, T, hop, window, _ptr(dy), _ptr(dw), _ptr(db),
+                Cout, ks, stride, pad, _ptr(dy_mask), dy_mask_slope, _ptr(ws), nws)
         return (dw, db) if with_bias else dw
 
     # ---------------------------------------------------------------- gemm
@@ -511,25 +526,12 @@ class HipKernels:
         """mode 0: a(M,K) b(N,K)^T (+bias[N]); 1: a(M,K) b(K,N); 2: a(K,M)^T b(K,N). out: write there (may alias
         out_mask: in-place masking)."""
         dev = _chk(a, b, bias, a_mask, out_mask, out)
-        if mode == 0:
-            M, K = a.shape
-            N, K2 = b.shape
-        elif mode == 1:
-            M, K = a.shape
-            K2, N = b.shape
-        else:
-            K, M = a.shape
-            K2, N = b.shape
-        assert K == K2, "gemm: inner dimension mismatch"
+        M, N, K = _gemm_shape(mode, a, b)
         c = torch.empty((M, N), dtype=torch.float32, device=dev) if out is None else out
         assert tuple(c.shape) == (M, N)
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_gemm_workspace_bytes', mode, M, N, K), dev)
-        with _on(dev):
-            rc = h.m2d_gemm(mode, _ptr(a), _ptr(b), _ptr(bias), _ptr(c), M, N, K, act, slope, _ptr(a_mask),
-                            a_mask_slope, _ptr(out_mask), out_mask_slope, _ptr(ws),
-                            0 if ws is None else ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_gemm")
+        ws, nws = _workspace(dev, 'm2d_gemm_workspace_bytes', mode, M, N, K)
+        _launch("m2d_gemm", dev, mode, _ptr(a), _ptr(b), _ptr(bias), _ptr(c), M, N, K, act, slope, _ptr(a_mask),
+                a_mask_slope, _ptr(out_mask), out_mask_slope, _ptr(ws), nws)
         return c
 
     @staticmethod
@@ -560,55 +562,37 @@ class HipKernels:
         out_mask the output's (it may BE the output: in-place masking). out: a view to write into."""
         dev = self._chk_rows(a, b, a_mask, out_mask, out)
         _chk(bias)
-        if mode == 0:
-            M, K = a.shape
-            N, K2 = b.shape
-        elif mode == 1:
-            M, K = a.shape
-            K2, N = b.shape
-        else:
-            K, M = a.shape
-            K2, N = b.shape
-        assert K == K2, "gemm: inner dimension mismatch"
+        M, N, K = _gemm_shape(mode, a, b)
         c = torch.empty((M, N), dtype=torch.float32, device=dev) if out is None else out
         assert tuple(c.shape) == (M, N)
         if a_mask is not None:
             assert a_mask.shape == a.shape and self._ld(a_mask) == self._ld(a)
         if out_mask is not None:
             assert out_mask.shape == c.shape and self._ld(out_mask) == self._ld(c)
-        ws = _ws(_ws_bytes('m2d_gemm_workspace_bytes', mode, M, N, K), dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_gemm_ld(mode, _ptr(a), self._ld(a), _ptr(b), self._ld(b), _ptr(bias), _ptr(c),
-                                        self._ld(c), M, N, K, act, slope, _ptr(a_mask), a_mask_slope, _ptr(out_mask),
-                                        out_mask_slope, _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_gemm_ld")
+        ws, nws = _workspace(dev, 'm2d_gemm_workspace_bytes', mode, M, N, K)
+        _launch("m2d_gemm_ld", dev, mode, _ptr(a), self._ld(a), _ptr(b), self._ld(b), _ptr(bias), _ptr(c), self._ld(c),
+                M, N, K, act, slope, _ptr(a_mask), a_mask_slope, _ptr(out_mask), out_mask_slope, _ptr(ws), nws)
         return c
 
     # ---------------------------------------------------------------- tanh heads
     def tanh_fwd(self, x):
         dev = _chk(x)
         y = torch.empty_like(x)
-        with _on(dev):
-            rc = _lib.lib().m2d_tanh_fwd(_ptr(x), _ptr(y), x.numel(), _stream(dev))
-        _lib.check(rc, "m2d_tanh_fwd")
+        _launch("m2d_tanh_fwd", dev, _ptr(x), _ptr(y), x.numel())
         return y
 
     def tanh_bwd(self, gy, y):
         """gy * (1 - y^2)"""
         dev = _chk(gy, y)
         gx = torch.empty_like(gy)
-        with _on(dev):
-            rc = _lib.lib().m2d_tanh_bwd(_ptr(gy), _ptr(y), _ptr(gx), gy.numel(), _stream(dev))
-        _lib.check(rc, "m2d_tanh_bwd")
+        _launch("m2d_tanh_bwd", dev, _ptr(gy), _ptr(y), _ptr(gx), gy.numel())
         return gx
 
     def tanh_bwd_bwd(self, g, gy, y):
         """-2 * y * g * gy: the gradient of tanh_bwd(gy, y) w.r.t. y for cotangent g"""
         dev = _chk(g, gy, y)
         out = torch.empty_like(y)
-        with _on(dev):
-            rc = _lib.lib().m2d_tanh_bwd_bwd(_ptr(g), _ptr(gy), _ptr(y), _ptr(out), y.numel(), _stream(dev))
-        _lib.check(rc, "m2d_tanh_bwd_bwd")
+        _launch("m2d_tanh_bwd_bwd", dev, _ptr(g), _ptr(gy), _ptr(y), _ptr(out), y.numel())
         return out
 
     def adam_multi(self, params, grads, exp_avgs, exp_avg_sqs, lr, beta1, beta2, eps, step, skip=None, repack=True):
@@ -620,49 +604,28 @@ class HipKernels:
             return
         dev = _chk(*params, *grads, *exp_avgs, *exp_avg_sqs, skip if torch.is_tensor(skip) else None)
         items = (_lib.AdamItem * len(params))()
-        stream = _stream(dev)
         keep = []
         for it, p, g, m, v in zip(items, params, grads, exp_avgs, exp_avg_sqs):
             assert p.numel() == g.numel() == m.numel() == v.numel()
             it.param, it.grad, it.exp_avg, it.exp_avg_sq, it.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-            ent = self._packed.get(id(p)) if (repack and p.dim() == 3) else None
+            key = (id(p), "conv")
+            ent = self._packed.get(key) if (repack and p.dim() == 3) else None
             if ent is not None and ent[0]() is p:
                 # written on THIS stream; consumers on other streams fork behind it (side.wait_stream(main) in the
                 # modules), so the refreshed entry is marked valid for every stream (None)
-                wf, wb = ent[3], ent[4]
+                wf, wb = ent[3]
                 it.pack_fwd, it.pack_bwd = wf.data_ptr(), wb.data_ptr()
                 it.cout, it.cin, it.ks = p.shape
-                keep.append((id(p), (ent[0], p._version, None, wf, wb)))
+                keep.append((key, (ent[0], p._version, None, ent[3])))
         bc1 = 1.0 - beta1 ** step
         bc2s = (1.0 - beta2 ** step) ** 0.5
-        with _on(dev):
-            rc = _lib.lib().m2d_adam_multi(ctypes.addressof(items), len(params), lr, beta1, beta2, eps, bc1, bc2s,
-                                           (skip if isinstance(skip, int) else _ptr(skip)) or 0, stream)
-        _lib.check(rc, "m2d_adam_multi")
+        _launch("m2d_adam_multi", dev, ctypes.addressof(items), len(params), lr, beta1, beta2, eps, bc1, bc2s,
+                (skip if isinstance(skip, int) else _ptr(skip)) or 0)
         for key, ent in keep:
             self._packed[key] = ent
         # (accumulated over the launches of one optimizer step - several step groups / 48-tensor batches - and consumed
         # by the invalidate_packed() that follows the step)
-        self._adam_kept = set(getattr(self, "_adam_kept", ())) | {k for k, _ in keep}
-
-    def transposed(self, w):
-        """w.t().contiguous() of a 2-D weight (the GRU kernels read W^T), kept like the packed conv images: built
-        once per weight tensor inside a weight_cache() scope, dropped by invalidate_packed()."""
-        stream = _stream(w.device)
-        key = (id(w), "T")
-        if self._cache_depth > 0:
-            ent = self._packed.get(key)
-            if ent is not None and ent[0]() is w and ent[1] == w._version and ent[2] == stream:
-                return ent[3]
-        wt = w.t().contiguous()
-        if self._cache_depth > 0:
-            packed = self._packed
-
-            def _drop(_ref, key=key):
-                packed.pop(key, None)
-
-            packed[key] = (weakref.ref(w, _drop), w._version, stream, wt)
-        return wt
+        self._adam_kept.update(k for k, _ in keep)
 
     # ---------------------------------------------------------------- critic iteration: pack + loss
     def pose_pack3(self, real, fake_rows, alpha, out=None):
@@ -671,9 +634,7 @@ class HipKernels:
         B, T, C = real.shape
         assert fake_rows.numel() == real.numel() and alpha.numel() == B
         o = torch.empty((3 * B, C, T), dtype=torch.float32, device=dev) if out is None else out
-        with _on(dev):
-            rc = _lib.lib().m2d_pose_pack3(_ptr(real), _ptr(fake_rows), _ptr(alpha), _ptr(o), B, T, C, _stream(dev))
-        _lib.check(rc, "m2d_pose_pack3")
+        _launch("m2d_pose_pack3", dev, _ptr(real), _ptr(fake_rows), _ptr(alpha), _ptr(o), B, T, C)
         return o
 
     def wgan_critic_loss(self, scores, B, pen0, pen1, gamma):
@@ -681,56 +642,44 @@ class HipKernels:
         dev = _chk(scores, pen0, pen1)
         assert scores.numel() == 3 * B
         out = torch.empty((3,), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_wgan_critic_loss(_ptr(scores), B, _ptr(pen0), _ptr(pen1), float(gamma), _ptr(out),
-                                                 _stream(dev))
-        _lib.check(rc, "m2d_wgan_critic_loss")
+        _launch("m2d_wgan_critic_loss", dev, _ptr(scores), B, _ptr(pen0), _ptr(pen1), float(gamma), _ptr(out))
         return out
 
     # ---------------------------------------------------------------- batch norm
     def channel_sums(self, x, mask=None, slope=0.0):
         """x: (B, C, L) or (B, C) -> (C,) sums over batch and length (optionally masked)."""
         dev = _chk(x, mask)
-        B, C = x.shape[0], x.shape[1]
-        L = x.shape[2] if x.dim() == 3 else 1
+        B, C, L = _bcl(x)
         out = torch.empty((C,), dtype=torch.float32, device=dev)
-        h = _lib.lib()
         scratch = _bn_scratch(dev, C)
         # no zero-kept scratch (C wider than the fixed one, or a capture that was not given one): the stateless
         # three-launch form needs its workspace (ADVICE r5: passing none made the call fail with "workspace too small")
-        ws = None if scratch is not None else _ws(_ws_bytes('m2d_bn_workspace_bytes', C), dev)
-        with _on(dev):
-            rc = h.m2d_channel_sums(_ptr(x), _ptr(mask), slope, _ptr(out), B, C, L, _ptr(ws),
-                                    0 if ws is None else ws.numel() * 4, _ptr(scratch), _stream(dev))
-        _lib.check(rc, "m2d_channel_sums")
+        ws, nws = (None, 0) if scratch is not None else _workspace(dev, 'm2d_bn_workspace_bytes', C)
+        _launch("m2d_channel_sums", dev, _ptr(x), _ptr(mask), slope, _ptr(out), B, C, L, _ptr(ws), nws, _ptr(scratch))
         return out
 
     @staticmethod
-    def _out_block(out, like):
-        """`out`: where a (B, C, L) result goes when it is a channel block of a wider buffer - a view shaped like the
-        result whose samples are out.stride(0) elements apart, dense inside a sample. -> (tensor, batch stride)"""
+    def _out_block(out, shape, dev):
+        """`out`: where a result of `shape` = (B, C, L) goes when it is a channel block of a wider buffer - a view
+        shaped like the result whose samples are out.stride(0) elements apart, dense inside a sample; None: a fresh
+        dense tensor. -> (tensor, batch stride; 0 = dense)"""
         if out is None:
-            return torch.empty_like(like), 0
-        assert out.shape == like.shape and out.dtype == torch.float32 and out.device == like.device
+            return torch.empty(shape, dtype=torch.float32, device=dev), 0
+        assert out.shape == shape and out.dtype == torch.float32 and out.device == dev
         assert out.dim() == 3 and out.stride(2) == 1 and out.stride(1) == out.shape[2] and out.stride(0) >= out.shape[1] * out.shape[2]
         return out, out.stride(0)
 
     def bn_fwd(self, x, gamma, beta, running_mean, running_var, training, eps, momentum, act=0, slope=0.0,
                residual=None, out=None):
         dev = _chk(x, gamma, beta, running_mean, running_var, residual)
-        B, C = x.shape[0], x.shape[1]
-        L = x.shape[2] if x.dim() == 3 else 1
-        y, ypitch = self._out_block(out, x)
+        B, C, L = _bcl(x)
+        y, ypitch = self._out_block(out, x.shape, dev)
         save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
         save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_bn_workspace_bytes', C), dev)
-        with _on(dev):
-            rc = h.m2d_bn_fwd_to(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(y),
-                                 _ptr(save_mean), _ptr(save_invstd), B, C, L, eps, momentum, 1 if training else 0,
-                                 act, slope, _ptr(residual), _ptr(ws), ws.numel() * 4,
-                                 _ptr(_bn_scratch(dev, C)) if training else 0, ypitch, _stream(dev))
-        _lib.check(rc, "m2d_bn_fwd")
+        ws, nws = _workspace(dev, 'm2d_bn_workspace_bytes', C)
+        _launch("m2d_bn_fwd_to", dev, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(y),
+                _ptr(save_mean), _ptr(save_invstd), B, C, L, eps, momentum, 1 if training else 0, act, slope,
+                _ptr(residual), _ptr(ws), nws, _ptr(_bn_scratch(dev, C)) if training else 0, ypitch)
         return y, save_mean, save_invstd
 
     @staticmethod
@@ -741,12 +690,9 @@ class HipKernels:
     def bn_stats(self, x):
         """(2C,) float64: per-channel sum and sum of squares of x (B, C[, L]) over batch and length."""
         dev = _chk(x)
-        B, C = x.shape[0], x.shape[1]
-        L = x.shape[2] if x.dim() == 3 else 1
+        B, C, L = _bcl(x)
         sums = torch.empty((2 * C,), dtype=torch.float64, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_bn_stats(_ptr(x), _ptr(sums), B, C, L, _ptr(_bn_scratch(dev, C)), _stream(dev))
-        _lib.check(rc, "m2d_bn_stats")
+        _launch("m2d_bn_stats", dev, _ptr(x), _ptr(sums), B, C, L, _ptr(_bn_scratch(dev, C)))
         return sums
 
     def bn_fwd_sums(self, x, sums, count, gamma, beta, running_mean, running_var, eps, momentum, act=0, slope=0.0,
@@ -754,18 +700,14 @@ class HipKernels:
         """Training forward from batch sums over `count` elements per channel (bn_stats, a conv's epilogue, or
         their all-reduce across data-parallel ranks). -> y, save_mean, save_invstd."""
         dev = _chk(x, gamma, beta, running_mean, running_var, residual)
-        B, C = x.shape[0], x.shape[1]
-        L = x.shape[2] if x.dim() == 3 else 1
+        B, C, L = _bcl(x)
         self._sums_ok(sums, C, dev)
-        y, ypitch = self._out_block(out, x)
+        y, ypitch = self._out_block(out, x.shape, dev)
         save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
         save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_bn_fwd_sums_to(_ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
-                                               _ptr(running_mean), _ptr(running_var), _ptr(y), _ptr(save_mean),
-                                               _ptr(save_invstd), B, C, L, eps, momentum, act, slope, _ptr(residual),
-                                               ypitch, _stream(dev))
-        _lib.check(rc, "m2d_bn_fwd_sums")
+        _launch("m2d_bn_fwd_sums_to", dev, _ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
+                _ptr(running_mean), _ptr(running_var), _ptr(y), _ptr(save_mean), _ptr(save_invstd), B, C, L, eps,
+                momentum, act, slope, _ptr(residual), ypitch)
         return y, save_mean, save_invstd
 
     def bn_update_running(self, sums, count, running_mean, running_var, eps, momentum):
@@ -774,10 +716,8 @@ class HipKernels:
         C = running_mean.numel()
         self._sums_ok(sums, C, dev)
         tmp = torch.empty((2 * C,), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_bn_update_running(_ptr(sums), float(count), _ptr(running_mean), _ptr(running_var),
-                                                  _ptr(tmp), C, eps, momentum, _stream(dev))
-        _lib.check(rc, "m2d_bn_update_running")
+        _launch("m2d_bn_update_running", dev, _ptr(sums), float(count), _ptr(running_mean), _ptr(running_var),
+                _ptr(tmp), C, eps, momentum)
 
     def bn_fwd_sums_pool(self, x, sums, count, gamma, beta, running_mean, running_var, eps, momentum, act=0, slope=0.0,
                          out=None):
@@ -786,16 +726,13 @@ class HipKernels:
         dev = _chk(x, gamma, beta, running_mean, running_var)
         B, C, L = x.shape
         self._sums_ok(sums, C, dev)
-        y, ypitch = self._out_block(out, x)
+        y, ypitch = self._out_block(out, x.shape, dev)
         pooled = torch.empty((B, C, L // 2), dtype=torch.float32, device=dev)
         save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
         save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_bn_fwd_sums_pool_to(_ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
-                                                    _ptr(running_mean), _ptr(running_var), _ptr(y), _ptr(pooled),
-                                                    _ptr(save_mean), _ptr(save_invstd), B, C, L, eps, momentum, act, slope,
-                                                    ypitch, _stream(dev))
-        _lib.check(rc, "m2d_bn_fwd_sums_pool_to")
+        _launch("m2d_bn_fwd_sums_pool_to", dev, _ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
+                _ptr(running_mean), _ptr(running_var), _ptr(y), _ptr(pooled), _ptr(save_mean), _ptr(save_invstd), B, C,
+                L, eps, momentum, act, slope, ypitch)
         return y, pooled, save_mean, save_invstd
 
     def bn_fwd_sums_upsample2(self, x, sums, count, gamma, beta, running_mean, running_var, eps, momentum, act=0, slope=0.0,
@@ -805,66 +742,45 @@ class HipKernels:
         dev = _chk(x, gamma, beta, running_mean, running_var)
         B, C, L = x.shape
         self._sums_ok(sums, C, dev)
-        if out is None:
-            up, pitch = torch.empty((B, C, 2 * L), dtype=torch.float32, device=dev), 0
-        else:
-            assert out.shape == (B, C, 2 * L) and out.dtype == torch.float32 and out.device == x.device
-            assert out.stride(2) == 1 and out.stride(1) == 2 * L and out.stride(0) >= 2 * C * L
-            up, pitch = out, out.stride(0)
+        up, pitch = self._out_block(out, (B, C, 2 * L), dev)
         save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
         save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_bn_fwd_sums_upsample2_to(_ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
-                                                         _ptr(running_mean), _ptr(running_var), _ptr(up), _ptr(save_mean),
-                                                         _ptr(save_invstd), B, C, L, eps, momentum, act, slope, pitch,
-                                                         _stream(dev))
-        _lib.check(rc, "m2d_bn_fwd_sums_upsample2_to")
+        _launch("m2d_bn_fwd_sums_upsample2_to", dev, _ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
+                _ptr(running_mean), _ptr(running_var), _ptr(up), _ptr(save_mean), _ptr(save_invstd), B, C, L, eps,
+                momentum, act, slope, pitch)
         return up, save_mean, save_invstd
 
     def bn_bwd_stats(self, dy, x, gamma, beta, save_mean, save_invstd, act=0, slope=0.0):
         """(2C,) float64: sum dz and sum dz * xhat, dz = dy * act'(bn(x))."""
         dev = _chk(dy, x, gamma, beta, save_mean, save_invstd)
-        B, C = x.shape[0], x.shape[1]
-        L = x.shape[2] if x.dim() == 3 else 1
+        B, C, L = _bcl(x)
         sums = torch.empty((2 * C,), dtype=torch.float64, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_bn_bwd_stats(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(save_mean),
-                                             _ptr(save_invstd), _ptr(sums), B, C, L, act, slope,
-                                             _ptr(_bn_scratch(dev, C)), _stream(dev))
-        _lib.check(rc, "m2d_bn_bwd_stats")
+        _launch("m2d_bn_bwd_stats", dev, _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(save_mean),
+                _ptr(save_invstd), _ptr(sums), B, C, L, act, slope, _ptr(_bn_scratch(dev, C)))
         return sums
 
     def bn_bwd_sums(self, dy, x, gamma, beta, save_mean, save_invstd, sums_local, sums_global, count, act=0, slope=0.0):
         dev = _chk(dy, x, gamma, beta, save_mean, save_invstd)
-        B, C = x.shape[0], x.shape[1]
-        L = x.shape[2] if x.dim() == 3 else 1
+        B, C, L = _bcl(x)
         self._sums_ok(sums_local, C, dev), self._sums_ok(sums_global, C, dev)
         dx = torch.empty_like(x)
         dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
         dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
-        ws = _ws(_ws_bytes('m2d_bn_workspace_bytes', C), dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_bn_bwd_sums(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(save_mean),
-                                            _ptr(save_invstd), _ptr(sums_local), _ptr(sums_global), float(count),
-                                            _ptr(dx), _ptr(dgamma), _ptr(dbeta), B, C, L, act, slope, _ptr(ws),
-                                            ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_bn_bwd_sums")
+        ws, nws = _workspace(dev, 'm2d_bn_workspace_bytes', C)
+        _launch("m2d_bn_bwd_sums", dev, _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(save_mean), _ptr(save_invstd),
+                _ptr(sums_local), _ptr(sums_global), float(count), _ptr(dx), _ptr(dgamma), _ptr(dbeta), B, C, L, act,
+                slope, _ptr(ws), nws)
         return dx, dgamma, dbeta
 
     def bn_bwd(self, dy, x, gamma, beta, save_mean, save_invstd, act=0, slope=0.0):
         dev = _chk(dy, x, gamma, beta, save_mean, save_invstd)
-        B, C = x.shape[0], x.shape[1]
-        L = x.shape[2] if x.dim() == 3 else 1
+        B, C, L = _bcl(x)
         dx = torch.empty_like(x)
         dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
         dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_bn_workspace_bytes', C), dev)
-        with _on(dev):
-            rc = h.m2d_bn_bwd(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(save_mean), _ptr(save_invstd),
-                              _ptr(dx), _ptr(dgamma), _ptr(dbeta), B, C, L, act, slope, _ptr(ws), ws.numel() * 4,
-                              _ptr(_bn_scratch(dev, C)), _stream(dev))
-        _lib.check(rc, "m2d_bn_bwd")
+        ws, nws = _workspace(dev, 'm2d_bn_workspace_bytes', C)
+        _launch("m2d_bn_bwd", dev, _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(save_mean), _ptr(save_invstd),
+                _ptr(dx), _ptr(dgamma), _ptr(dbeta), B, C, L, act, slope, _ptr(ws), nws, _ptr(_bn_scratch(dev, C)))
         return dx, dgamma, dbeta
 
     # ---------------------------------------------------------------- GRU
@@ -877,13 +793,9 @@ class HipKernels:
         saved = None
         if save:
             saved = torch.empty((4, B, T, H), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        with _on(dev):
-            rc = h.m2d_gru_layer_fwd(_ptr(gi), _ptr(w_hh_t), _ptr(b_hh), _ptr(lengths), _ptr(out),
-                                     _ptr(saved[0]) if save else 0, _ptr(saved[1]) if save else 0,
-                                     _ptr(saved[2]) if save else 0, _ptr(saved[3]) if save else 0, B, T, H,
-                                     _stream(dev))
-        _lib.check(rc, "m2d_gru_layer_fwd")
+        _launch("m2d_gru_layer_fwd", dev, _ptr(gi), _ptr(w_hh_t), _ptr(b_hh), _ptr(lengths), _ptr(out),
+                _ptr(saved[0]) if save else 0, _ptr(saved[1]) if save else 0, _ptr(saved[2]) if save else 0,
+                _ptr(saved[3]) if save else 0, B, T, H)
         return out, saved
 
     def gru_layer_bwd(self, dout, out, saved, w_hh, lengths=None):
@@ -892,12 +804,8 @@ class HipKernels:
         dgi = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
         dgh = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
         dh_buf = torch.empty((2, B, H), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        with _on(dev):
-            rc = h.m2d_gru_layer_bwd(_ptr(dout), _ptr(out), _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]),
-                                     _ptr(saved[3]), _ptr(w_hh), _ptr(lengths), _ptr(dgi), _ptr(dgh),
-                                     _ptr(dh_buf), B, T, H, _stream(dev))
-        _lib.check(rc, "m2d_gru_layer_bwd")
+        _launch("m2d_gru_layer_bwd", dev, _ptr(dout), _ptr(out), _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]),
+                _ptr(saved[3]), _ptr(w_hh), _ptr(lengths), _ptr(dgi), _ptr(dgh), _ptr(dh_buf), B, T, H)
         return dgi, dgh
 
     @staticmethod
@@ -921,10 +829,8 @@ class HipKernels:
         out = torch.empty((B, T, H), dtype=torch.float32, device=dev) if (with_out or save) else None
         h_n = torch.empty((B, H), dtype=torch.float32, device=dev)
         saved = torch.empty((4, B, T, H), dtype=torch.float32, device=dev) if save else None
-        with _on(dev):
-            rc = _lib.lib().m2d_gru_small_fwd(_ptr(gi), _ptr(w_hh), _ptr(b_hh), _ptr(lengths), _ptr(out), _ptr(h_n),
-                                              _ptr(saved), B, T, H, _stream(dev))
-        _lib.check(rc, "m2d_gru_small_fwd")
+        _launch("m2d_gru_small_fwd", dev, _ptr(gi), _ptr(w_hh), _ptr(b_hh), _ptr(lengths), _ptr(out), _ptr(h_n),
+                _ptr(saved), B, T, H)
         return out, h_n, saved
 
     def gru_small_bwd(self, dout, dh_n, out, saved, w_hh, lengths=None):
@@ -934,10 +840,8 @@ class HipKernels:
         self._chk_lengths(lengths, dev, B)
         dgi = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
         dgh = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_gru_small_bwd(_ptr(dout), _ptr(dh_n), _ptr(out), _ptr(saved), _ptr(w_hh),
-                                              _ptr(lengths), _ptr(dgi), _ptr(dgh), B, T, H, _stream(dev))
-        _lib.check(rc, "m2d_gru_small_bwd")
+        _launch("m2d_gru_small_bwd", dev, _ptr(dout), _ptr(dh_n), _ptr(out), _ptr(saved), _ptr(w_hh), _ptr(lengths),
+                _ptr(dgi), _ptr(dgh), B, T, H)
         return dgi, dgh
 
     @staticmethod
@@ -968,19 +872,15 @@ class HipKernels:
         sv = self._ptr_array(saved) if save else (None, None)
         hz = self._ptr_array(h0) if h0 is not None else (None, None)
         hn = self._ptr_array(list(h_n.unbind(0))) if want_state else (None, None)
-        h = _lib.lib()
         # scratch for the persistent form (one launch for the whole recurrence); the library decides
-        counters = (torch.empty((h.m2d_gru_stack_counters(B, L),), dtype=torch.int32, device=dev)
+        counters = (torch.empty((_lib.lib().m2d_gru_stack_counters(B, L),), dtype=torch.int32, device=dev)
                     if (persistent and self.persistent_gru) else None)
-        with _on(dev):
-            if state:
-                rc = h.m2d_gru_stack_fwd_state(_ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
-                                               sv[1], _ptr(lengths), hz[1], hn[1], B, T, H, L, _ptr(counters),
-                                               _stream(dev))
-            else:
-                rc = h.m2d_gru_stack_fwd(_ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
-                                         sv[1], _ptr(lengths), B, T, H, L, _ptr(counters), _stream(dev))
-        _lib.check(rc, "m2d_gru_stack_fwd_state" if state else "m2d_gru_stack_fwd")
+        if state:
+            _launch("m2d_gru_stack_fwd_state", dev, _ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1],
+                    keep[4][1], sv[1], _ptr(lengths), hz[1], hn[1], B, T, H, L, _ptr(counters))
+        else:
+            _launch("m2d_gru_stack_fwd", dev, _ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
+                    sv[1], _ptr(lengths), B, T, H, L, _ptr(counters))
         return (outs, saved, h_n) if want_state else (outs, saved)
 
     @staticmethod
@@ -1004,9 +904,7 @@ class HipKernels:
     @staticmethod
     def fault_fetch(dst):
         """dst[0] (device float) = 1.0 when that word is raised, else 0.0, on the current stream (dp.GradExchange)"""
-        dev = _chk(dst)
-        with _on(dev):
-            _lib.check(_lib.lib().m2d_fault_fetch(_ptr(dst), _stream(dev)), "m2d_fault_fetch")
+        _launch("m2d_fault_fetch", _chk(dst), _ptr(dst))
 
     @staticmethod
     def raise_async_fault():
@@ -1038,13 +936,10 @@ class HipKernels:
         dgh = [torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev) for _ in range(L)]
         dhb = [torch.empty((2, B, H), dtype=torch.float32, device=dev) for _ in range(L)]
         keep = [self._ptr_array(v) for v in (outs, saved, w_hh, w_ih, dgi, dgh, dhb)]
-        h = _lib.lib()
-        counters = (torch.empty((h.m2d_gru_stack_counters(B, L),), dtype=torch.int32, device=dev)
+        counters = (torch.empty((_lib.lib().m2d_gru_stack_counters(B, L),), dtype=torch.int32, device=dev)
                     if (persistent and self.persistent_gru) else None)
-        with _on(dev):
-            rc = h.m2d_gru_stack_bwd(_ptr(dout), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
-                                     keep[5][1], keep[6][1], _ptr(lengths), B, T, H, L, _ptr(counters), _stream(dev))
-        _lib.check(rc, "m2d_gru_stack_bwd")
+        _launch("m2d_gru_stack_bwd", dev, _ptr(dout), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
+                keep[5][1], keep[6][1], _ptr(lengths), B, T, H, L, _ptr(counters))
         return dgi, dgh
 
     # ---------------------------------------------------------------- gradient penalty
@@ -1053,9 +948,7 @@ class HipKernels:
         dev = _chk(real, fake, alpha)
         B, n = real.shape
         out = torch.empty_like(real)
-        with _on(dev):
-            rc = _lib.lib().m2d_gp_interpolate(_ptr(real), _ptr(fake), _ptr(alpha), _ptr(out), B, n, _stream(dev))
-        _lib.check(rc, "m2d_gp_interpolate")
+        _launch("m2d_gp_interpolate", dev, _ptr(real), _ptr(fake), _ptr(alpha), _ptr(out), B, n)
         return out
 
     def gp_penalty_fwd(self, g, lp):
@@ -1063,12 +956,8 @@ class HipKernels:
         B, n = g.shape
         norms = torch.empty((B,), dtype=torch.float32, device=dev)
         pen = torch.empty((), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_gp_penalty_workspace_bytes', B), dev)
-        with _on(dev):
-            rc = h.m2d_gp_penalty_fwd(_ptr(g), _ptr(norms), _ptr(pen), B, n, 1 if lp else 0, _ptr(ws),
-                                      ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_gp_penalty_fwd")
+        ws, nws = _workspace(dev, 'm2d_gp_penalty_workspace_bytes', B)
+        _launch("m2d_gp_penalty_fwd", dev, _ptr(g), _ptr(norms), _ptr(pen), B, n, 1 if lp else 0, _ptr(ws), nws)
         return pen, norms
 
     def gp_penalty_bwd(self, g, norms, gout, lp, out=None):
@@ -1076,61 +965,40 @@ class HipKernels:
         B, n = g.shape
         dg = torch.empty_like(g) if out is None else out
         assert dg.numel() == g.numel()
-        with _on(dev):
-            rc = _lib.lib().m2d_gp_penalty_bwd(_ptr(g), _ptr(norms), _ptr(gout), _ptr(dg), B, n, 1 if lp else 0,
-                                               _stream(dev))
-        _lib.check(rc, "m2d_gp_penalty_bwd")
+        _launch("m2d_gp_penalty_bwd", dev, _ptr(g), _ptr(norms), _ptr(gout), _ptr(dg), B, n, 1 if lp else 0)
         return dg
 
     # ---------------------------------------------------------------- losses
     def l1_mean_fwd(self, a, b):
         dev = _chk(a, b)
         out = torch.empty((), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_reduce_workspace_bytes', ), dev)
-        with _on(dev):
-            rc = h.m2d_l1_mean_fwd(_ptr(a), _ptr(b), _ptr(out), a.numel(), _ptr(ws), ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_l1_mean_fwd")
+        ws, nws = _workspace(dev, 'm2d_reduce_workspace_bytes')
+        _launch("m2d_l1_mean_fwd", dev, _ptr(a), _ptr(b), _ptr(out), a.numel(), _ptr(ws), nws)
         return out
 
     def l1_mean_bwd(self, a, b, gout):
         dev = _chk(a, b, gout)
         da = torch.empty_like(a)
-        with _on(dev):
-            rc = _lib.lib().m2d_l1_mean_bwd(_ptr(a), _ptr(b), _ptr(gout), _ptr(da), a.numel(), _stream(dev))
-        _lib.check(rc, "m2d_l1_mean_bwd")
+        _launch("m2d_l1_mean_bwd", dev, _ptr(a), _ptr(b), _ptr(gout), _ptr(da), a.numel())
         return da
-
-    @staticmethod
-    def _chk_labels(labels, dev, B):
-        if not labels.is_cuda or labels.device != dev or labels.dtype != torch.int64 or not labels.is_contiguous():
-            raise _lib.M2dError("cross entropy: labels must be a contiguous int64 tensor on %s" % dev)
-        if labels.numel() != B:
-            raise _lib.M2dError("cross entropy: %d labels for %d rows" % (labels.numel(), B))
 
     def cross_entropy_fwd(self, logits, labels, with_pred=False):
         """mean softmax cross-entropy of (B, C) logits against int64 labels -> (0-dim loss, int64 argmax or None)"""
         dev = _chk(logits)
         B, C = logits.shape
-        self._chk_labels(labels, dev, B)
+        _chk_labels(labels, dev, B, "cross entropy")
         loss = torch.empty((), dtype=torch.float32, device=dev)
         pred = torch.empty((B,), dtype=torch.int64, device=dev) if with_pred else None
-        ws = _ws(_ws_bytes('m2d_cross_entropy_workspace_bytes', B, C), dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_cross_entropy_fwd(_ptr(logits), _ptr(labels), _ptr(loss), _ptr(pred), B, C, _ptr(ws),
-                                                  0 if ws is None else ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_cross_entropy_fwd")
+        ws, nws = _workspace(dev, 'm2d_cross_entropy_workspace_bytes', B, C)
+        _launch("m2d_cross_entropy_fwd", dev, _ptr(logits), _ptr(labels), _ptr(loss), _ptr(pred), B, C, _ptr(ws), nws)
         return loss, pred
 
     def cross_entropy_bwd(self, logits, labels, gout):
         dev = _chk(logits, gout)
         B, C = logits.shape
-        self._chk_labels(labels, dev, B)
+        _chk_labels(labels, dev, B, "cross entropy")
         dlogits = torch.empty_like(logits)
-        with _on(dev):
-            rc = _lib.lib().m2d_cross_entropy_bwd(_ptr(logits), _ptr(labels), _ptr(gout), _ptr(dlogits), B, C,
-                                                  _stream(dev))
-        _lib.check(rc, "m2d_cross_entropy_bwd")
+        _launch("m2d_cross_entropy_bwd", dev, _ptr(logits), _ptr(labels), _ptr(gout), _ptr(dlogits), B, C)
         return dlogits
 
     @staticmethod
@@ -1146,10 +1014,7 @@ class HipKernels:
         self._chk_bce(x, n0, n1)
         out = torch.empty((3,), dtype=torch.float32, device=dev)
         dx = torch.empty_like(x) if with_dx else None
-        with _on(dev):
-            rc = _lib.lib().m2d_bce_logits_fwd(_ptr(x), int(n0), float(t0), int(n1), float(t1), _ptr(out), _ptr(dx),
-                                               _stream(dev))
-        _lib.check(rc, "m2d_bce_logits_fwd")
+        _launch("m2d_bce_logits_fwd", dev, _ptr(x), int(n0), float(t0), int(n1), float(t1), _ptr(out), _ptr(dx))
         return out, dx
 
     def bce_logits_bwd(self, x, n0, t0, n1, t1, gout):
@@ -1157,23 +1022,15 @@ class HipKernels:
         dev = _chk(x, gout)
         self._chk_bce(x, n0, n1)
         dx = torch.empty_like(x)
-        with _on(dev):
-            rc = _lib.lib().m2d_bce_logits_bwd(_ptr(x), int(n0), float(t0), int(n1), float(t1), _ptr(gout), _ptr(dx),
-                                               _stream(dev))
-        _lib.check(rc, "m2d_bce_logits_bwd")
+        _launch("m2d_bce_logits_bwd", dev, _ptr(x), int(n0), float(t0), int(n1), float(t1), _ptr(gout), _ptr(dx))
         return dx
 
     # ---------------------------------------------------------------- label conditioning and dropout (cond.hip)
-    @staticmethod
-    def _chk_class_indices(labels, n, dev):
-        if labels.dtype != torch.int64 or not labels.is_contiguous() or labels.numel() != n or labels.device != dev:
-            raise _lib.M2dError("labels: %d contiguous int64 values on %s expected" % (n, dev))
-
     def label_concat(self, x, E, labels, layout, out=None):
         """[x | E[labels[b]]]: layout 0 x (B, T, C) -> (B, T, C + D); layout 1 x (B, C, T) -> (B, C + D, T)"""
         dev = _chk(x, E, out)
         B = x.shape[0]
-        self._chk_class_indices(labels, B, dev)
+        _chk_labels(labels, dev, B, "label_concat")
         L, D = E.shape
         if layout == 0:
             T, C = x.shape[1], x.shape[2]
@@ -1183,10 +1040,7 @@ class HipKernels:
             shape = (B, C + D, T)
         o = torch.empty(shape, dtype=torch.float32, device=dev) if out is None else out
         assert tuple(o.shape) == shape
-        with _on(dev):
-            rc = _lib.lib().m2d_label_concat(_ptr(x), _ptr(E), _ptr(labels), _ptr(o), B, T, C, L, D, int(layout),
-                                             _stream(dev))
-        _lib.check(rc, "m2d_label_concat")
+        _launch("m2d_label_concat", dev, _ptr(x), _ptr(E), _ptr(labels), _ptr(o), B, T, C, L, D, int(layout))
         return o
 
     def pose_pack3_label(self, real, fake_rows, alpha, E, real_lbl, fake_lbl, out=None):
@@ -1196,28 +1050,24 @@ class HipKernels:
         B, T, C = real.shape
         L, D = E.shape
         assert fake_rows.numel() == real.numel() and alpha.numel() == B
-        self._chk_class_indices(real_lbl, B, dev)
-        self._chk_class_indices(fake_lbl, B, dev)
+        _chk_labels(real_lbl, dev, B, "pose_pack3_label")
+        _chk_labels(fake_lbl, dev, B, "pose_pack3_label")
         o = torch.empty((3 * B, C + D, T), dtype=torch.float32, device=dev) if out is None else out
         assert tuple(o.shape) == (3 * B, C + D, T)
-        with _on(dev):
-            rc = _lib.lib().m2d_pose_pack3_label(_ptr(real), _ptr(fake_rows), _ptr(alpha), _ptr(E), _ptr(real_lbl),
-                                                 _ptr(fake_lbl), _ptr(o), B, T, C, L, D, _stream(dev))
-        _lib.check(rc, "m2d_pose_pack3_label")
+        _launch("m2d_pose_pack3_label", dev, _ptr(real), _ptr(fake_rows), _ptr(alpha), _ptr(E), _ptr(real_lbl),
+                _ptr(fake_lbl), _ptr(o), B, T, C, L, D)
         return o
 
     def label_embed_bwd(self, dx, labels, r0, r1, c0, L, D, layout, out=None):
         """dE (L, D) = per class, the sum over rows [r0, r1) carrying it (labels: one per row of the range) of
         dx[row, c0:c0 + D, :] summed over time; layout 0: dx (R, T, Ctot), layout 1: dx (R, Ctot, T)"""
         dev = _chk(dx, out)
-        self._chk_class_indices(labels, r1 - r0, dev)
+        _chk_labels(labels, dev, r1 - r0, "label_embed_bwd")
         assert 0 <= r0 < r1 <= dx.shape[0]
         T, Ctot = (dx.shape[1], dx.shape[2]) if layout == 0 else (dx.shape[2], dx.shape[1])
         o = torch.empty((L, D), dtype=torch.float32, device=dev) if out is None else out
-        with _on(dev):
-            rc = _lib.lib().m2d_label_embed_bwd(_ptr(dx), _ptr(labels), _ptr(o), int(r0), int(r1), T, Ctot, int(c0),
-                                                int(L), int(D), int(layout), _stream(dev))
-        _lib.check(rc, "m2d_label_embed_bwd")
+        _launch("m2d_label_embed_bwd", dev, _ptr(dx), _ptr(labels), _ptr(o), int(r0), int(r1), T, Ctot, int(c0),
+                int(L), int(D), int(layout))
         return o
 
     def randn_frames(self, seed, frame0, B, n, C, device, out=None):
@@ -1226,10 +1076,7 @@ class HipKernels:
         dev = _chk(o)
         if tuple(o.shape) != (B, n, C) or o.dtype != torch.float32 or not o.is_contiguous():
             raise _lib.M2dError("randn_frames: out must be a contiguous float32 (%d, %d, %d) tensor" % (B, n, C))
-        with _on(dev):
-            rc = _lib.lib().m2d_randn_frames(_ptr(o), int(seed) & 0xFFFFFFFFFFFFFFFF, int(frame0), int(B), int(n),
-                                             int(C), _stream(dev))
-        _lib.check(rc, "m2d_randn_frames")
+        _launch("m2d_randn_frames", dev, _ptr(o), int(seed) & 0xFFFFFFFFFFFFFFFF, int(frame0), int(B), int(n), int(C))
         return o
 
     def render_sticks(self, poses, height, width, out=None):
@@ -1245,9 +1092,7 @@ class HipKernels:
         if (not o.is_cuda or o.device != dev or o.dtype != torch.uint8 or tuple(o.shape) != shape
                 or not o.is_contiguous()):
             raise _lib.M2dError("render_sticks: out must be a contiguous uint8 %s tensor on %s" % (shape, dev))
-        with _on(dev):
-            rc = _lib.lib().m2d_render_sticks(_ptr(poses), n, int(height), int(width), _ptr(o), _stream(dev))
-        _lib.check(rc, "m2d_render_sticks")
+        _launch("m2d_render_sticks", dev, _ptr(poses), n, int(height), int(width), _ptr(o))
         return o
 
     def dropout(self, x, mask, p_keep=0.5, scale=2.0, seed=None, offset=0, out=None):
@@ -1265,43 +1110,33 @@ class HipKernels:
             raise _lib.M2dError("dropout: a mask or a seed is needed")
         n = x.numel() if x is not None else mask.numel()
         y = (torch.empty_like(x) if out is None else out) if x is not None else None
-        with _on(dev):
-            rc = _lib.lib().m2d_dropout(_ptr(x), _ptr(y), _ptr(mask), n, float(p_keep), float(scale),
-                                        int(seed or 0) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, int(gen),
-                                        _stream(dev))
-        _lib.check(rc, "m2d_dropout")
+        _launch("m2d_dropout", dev, _ptr(x), _ptr(y), _ptr(mask), n, float(p_keep), float(scale),
+                int(seed or 0) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, int(gen))
         return y if x is not None else mask
+
+    @staticmethod
+    def _strided_mean(name, x, B, C, T, sb, sc, st):
+        """A 0-dim mean over the (B, C, T) view, with element strides (sb, sc, st), of storage `x` (entry point `name`)"""
+        dev = _chk(x)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        ws, nws = _workspace(dev, 'm2d_reduce_workspace_bytes')
+        _launch(name, dev, _ptr(x), _ptr(out), B, C, T, sb, sc, st, _ptr(ws), nws)
+        return out
 
     def tv_mean_fwd(self, x, B, C, T, sb, sc, st):
         """x: storage holding a (B, C, T) view with element strides (sb, sc, st)."""
-        dev = _chk(x)
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_reduce_workspace_bytes', ), dev)
-        with _on(dev):
-            rc = h.m2d_tv_mean_fwd(_ptr(x), _ptr(out), B, C, T, sb, sc, st, _ptr(ws), ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_tv_mean_fwd")
-        return out
+        return self._strided_mean("m2d_tv_mean_fwd", x, B, C, T, sb, sc, st)
 
     def tv_mean_bwd(self, x, gout, B, C, T, sb, sc, st):
         dev = _chk(x, gout)
         dx = torch.empty_like(x)
-        with _on(dev):
-            rc = _lib.lib().m2d_tv_mean_bwd(_ptr(x), _ptr(gout), _ptr(dx), B, C, T, sb, sc, st, _stream(dev))
-        _lib.check(rc, "m2d_tv_mean_bwd")
+        _launch("m2d_tv_mean_bwd", dev, _ptr(x), _ptr(gout), _ptr(dx), B, C, T, sb, sc, st)
         return dx
 
     # ---------------------------------------------------------------- evaluation metric, dataset scaling
     def jerk_mean_fwd(self, x, B, C, T, sb, sc, st):
         """jerkiness of the (B, C, T) view (element strides sb, sc, st) of storage `x` -> 0-dim."""
-        dev = _chk(x)
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        ws = _ws(_ws_bytes('m2d_reduce_workspace_bytes', ), dev)
-        with _on(dev):
-            rc = h.m2d_jerk_mean_fwd(_ptr(x), _ptr(out), B, C, T, sb, sc, st, _ptr(ws), ws.numel() * 4, _stream(dev))
-        _lib.check(rc, "m2d_jerk_mean_fwd")
-        return out
+        return self._strided_mean("m2d_jerk_mean_fwd", x, B, C, T, sb, sc, st)
 
     def affine_cols(self, x, scale, shift, out=None):
         """x (..., cols) * scale[cols] + shift[cols] (MinMaxScaler transform / inverse); out may be x."""
@@ -1309,62 +1144,47 @@ class HipKernels:
         cols = x.shape[-1]
         assert scale.numel() == cols and shift.numel() == cols
         y = torch.empty_like(x) if out is None else out
-        with _on(dev):
-            rc = _lib.lib().m2d_affine_cols(_ptr(x), _ptr(scale), _ptr(shift), _ptr(y), x.numel() // max(cols, 1), cols,
-                                            _stream(dev))
-        _lib.check(rc, "m2d_affine_cols")
+        _launch("m2d_affine_cols", dev, _ptr(x), _ptr(scale), _ptr(shift), _ptr(y), x.numel() // max(cols, 1), cols)
         return y
 
     # ---------------------------------------------------------------- U-Net resampling
     def maxpool2_fwd(self, x):
         """x: (B, C, L) dense, or a channel block of a wider buffer (samples x.stride(0) apart, dense inside)"""
         B, C, L = x.shape
-        if not x.is_contiguous() and x.stride(2) == 1 and x.stride(1) == L and x.stride(0) > C * L and x.is_cuda \
-                and x.dtype == torch.float32 and L % 2 == 0 and (C * L) % 8 == 0 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0:
+        block = (not x.is_contiguous() and x.stride(2) == 1 and x.stride(1) == L and x.stride(0) > C * L and x.is_cuda
+                 and x.dtype == torch.float32 and L % 2 == 0 and (C * L) % 8 == 0 and x.stride(0) % 4 == 0
+                 and x.data_ptr() % 16 == 0)
+        if block:
             dev = x.device
-            y = torch.empty((B, C, L // 2), dtype=torch.float32, device=dev)
-            with _on(dev):
-                rc = _lib.lib().m2d_maxpool2_fwd_from(_ptr(x), _ptr(y), B, C, L, x.stride(0), _stream(dev))
-            _lib.check(rc, "m2d_maxpool2_fwd_from")
-            return y
-        x = x if x.is_contiguous() else x.contiguous()
-        dev = _chk(x)
+        else:
+            x = x if x.is_contiguous() else x.contiguous()
+            dev = _chk(x)
         y = torch.empty((B, C, L // 2), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_maxpool2_fwd(_ptr(x), _ptr(y), B * C, L, _stream(dev))
-        _lib.check(rc, "m2d_maxpool2_fwd")
+        if block:
+            _launch("m2d_maxpool2_fwd_from", dev, _ptr(x), _ptr(y), B, C, L, x.stride(0))
+        else:
+            _launch("m2d_maxpool2_fwd", dev, _ptr(x), _ptr(y), B * C, L)
         return y
 
     def maxpool2_bwd(self, x, dy):
         dev = _chk(x, dy)
         B, C, L = x.shape
         dx = torch.empty_like(x)
-        with _on(dev):
-            rc = _lib.lib().m2d_maxpool2_bwd(_ptr(x), _ptr(dy), _ptr(dx), B * C, L, _stream(dev))
-        _lib.check(rc, "m2d_maxpool2_bwd")
+        _launch("m2d_maxpool2_bwd", dev, _ptr(x), _ptr(dy), _ptr(dx), B * C, L)
         return dx
 
     def upsample2_fwd(self, x, out=None):
         dev = _chk(x)
         B, C, L = x.shape
-        if out is None:
-            y, ypitch = torch.empty((B, C, 2 * L), dtype=torch.float32, device=dev), 0
-        else:
-            assert tuple(out.shape) == (B, C, 2 * L) and out.dtype == torch.float32 and out.device == dev
-            assert out.stride(2) == 1 and out.stride(1) == 2 * L and out.stride(0) >= 2 * C * L
-            y, ypitch = out, out.stride(0)
-        with _on(dev):
-            rc = _lib.lib().m2d_upsample2_fwd_to(_ptr(x), _ptr(y), B, C, L, ypitch, _stream(dev))
-        _lib.check(rc, "m2d_upsample2_fwd")
+        y, ypitch = self._out_block(out, (B, C, 2 * L), dev)
+        _launch("m2d_upsample2_fwd_to", dev, _ptr(x), _ptr(y), B, C, L, ypitch)
         return y
 
     def upsample2_bwd(self, dy):
         dev = _chk(dy)
         B, C, Lo = dy.shape
         dx = torch.empty((B, C, Lo // 2), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = _lib.lib().m2d_upsample2_bwd(_ptr(dy), _ptr(dx), B * C, Lo // 2, _stream(dev))
-        _lib.check(rc, "m2d_upsample2_bwd")
+        _launch("m2d_upsample2_bwd", dev, _ptr(dy), _ptr(dx), B * C, Lo // 2)
         return dx
 
     # ---------------------------------------------------------------- profiler
