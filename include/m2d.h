@@ -436,6 +436,20 @@ int m2d_randn_frames(float* out, unsigned long long seed, long long frame0, int 
  * height, width in [1, 4096]; n_frames 0: nothing to do. Deterministic, no atomics. */
 int m2d_render_sticks(const float* poses, long n_frames, int height, int width, unsigned char* out, void* stream);
 
+/* ---- polyphase FIR resampling of audio rows (change_rate.py:6-8: the reference shells out to sox) -----------------
+ * Row b of x (B rows, ldx floats apart) holds the samples with ABSOLUTE indices [x0, x0 + nx); every other sample is
+ * zero. half = (ntaps - 1) / 2 (ntaps odd, <= 16384). For output index n in [n0, n0 + ny), with t = n down + half:
+ *   y[b ldy + n - n0] = sum over all integers m with 0 <= t - m up < ntaps of taps[t - m up] X_b[m]
+ * = scipy.signal.resample_poly(x, up, down, window=taps / up, padtype='constant'): zero phase, output n sits at input
+ * time n down / up. up / down must be reduced by their gcd. All index arithmetic is 64-bit (n down may pass 2^32;
+ * n down + half must stay below 2^63). The value of output n is a bit-level pure function of n, the taps and the
+ * samples of its window - one fp32 accumulator, fmaf over its taps in ascending tap index (descending m) - and does not
+ * depend on n0, x0, ny, nx, the launch's tiling or B: the chunks of a stream equal the whole-track call bit for bit.
+ * M2D_ERR_ARG (nothing launched): up, down or B <= 0; nx, ny, x0 or n0 < 0; even ntaps or ntaps > 16384; ldx < nx or
+ * ldy < ny; an unreduced ratio. ny == 0: nothing to do. */
+int m2d_resample_poly(const float* x, long long x0, int nx, long long ldx, const float* taps, int ntaps, int up,
+                      int down, float* y, long long n0, int ny, long long ldy, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

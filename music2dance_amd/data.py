@@ -159,6 +159,28 @@ def get_positions(sequence, length=120):
     return s, s + length
 
 
+def retime_sequence(frames, new_len):
+    """A take of len(frames) frames re-timed to new_len frames by linear interpolation, host fp64 - the recipe in the
+    comment of the reference's utils.interpolate (utils.py:257-264), which its README asks for on the waltz takes:
+    out[i] = interpolate(frames, i delta), delta = (len - 1) / (new_len - 1); interpolate(x, fi) = x[i] when the
+    fraction f = fi - int(fi) is below machine epsilon, else x[i] + f (x[i + 1] - x[i]). The last output is the last
+    frame: where rounding leaves i delta a hair off len - 1 the reference reads x[len]; here the position is clamped."""
+    x = np.asarray(frames, dtype=np.float64)
+    n, new_len = len(x), int(new_len)
+    if n < 1 or new_len < 1:
+        raise ValueError("retime_sequence: a take of at least one frame and new_len >= 1 expected")
+    if new_len == 1 or n == 1:
+        return np.repeat(x[:1], new_len, axis=0)
+    delta = (n - 1) / float(new_len - 1)
+    pos = np.minimum(np.arange(new_len) * delta, float(n - 1))
+    pos[-1] = n - 1
+    i = pos.astype(np.int64)
+    f = pos - i
+    nxt = np.minimum(i + 1, n - 1)
+    f = f.reshape((-1,) + (1,) * (x.ndim - 1))
+    return np.where(f < np.finfo(np.float64).eps, x[i], x[i] + f * (x[nxt] - x[i]))
+
+
 # --------------------------------------------------------------------------------------- datasets
 # Storage is columnar: every take of a dataset lives in ONE array, takes back to back, with an offsets table - poses
 # (sum of frames, 23, 3) and audio (sum of samples,). `sequences` / `musics` hand out per-take views of those arrays

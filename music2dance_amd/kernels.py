@@ -1095,6 +1095,42 @@ class HipKernels:
         _launch("m2d_render_sticks", dev, _ptr(poses), n, int(height), int(width), _ptr(o))
         return o
 
+    @staticmethod
+    def _chk_audio_rows(t, what):
+        """fp32 rows on a HIP device, unit stride inside a row (a column slice of a wider buffer is fine) -> leading
+        dimension"""
+        if not t.is_cuda:
+            raise _lib.M2dError("m2d kernels need HIP device tensors (got %s); there is no CPU path" % t.device)
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise _lib.M2dError("resample_poly: %s must be a 2-D float32 tensor" % what)
+        B, n = t.shape
+        if n > 1 and t.stride(1) != 1:
+            raise _lib.M2dError("resample_poly: the rows of %s must be dense" % what)
+        ld = t.stride(0) if B > 1 and n > 0 else n
+        if ld < n:
+            raise _lib.M2dError("resample_poly: overlapping rows in %s" % what)
+        return ld
+
+    def resample_poly(self, x, x0, taps, up, down, n0, ny, out=None):
+        """Outputs [n0, n0 + ny) of the polyphase resampling by up / down of rows x (B, nx) that hold the samples with
+        absolute indices [x0, x0 + nx) (zeros elsewhere) -> (B, ny); taps: odd-length fp32 filter (m2d_resample_poly:
+        y[n] = sum_m taps[n down + half - m up] x[m], bit-identical however a track is cut into calls)"""
+        ldx = self._chk_audio_rows(x, "x")
+        dev = _chk(taps)
+        if taps.dim() != 1 or taps.device != x.device:
+            raise _lib.M2dError("resample_poly: taps must be a 1-D tensor on %s" % x.device)
+        B, nx = x.shape
+        ny = int(ny)
+        if ny < 0:
+            raise _lib.M2dError("resample_poly: ny < 0")
+        o = torch.empty((B, ny), dtype=torch.float32, device=dev) if out is None else out
+        ldy = self._chk_audio_rows(o, "out")
+        if o.device != dev or tuple(o.shape) != (B, ny):
+            raise _lib.M2dError("resample_poly: out must be a (%d, %d) tensor on %s" % (B, ny, dev))
+        _launch("m2d_resample_poly", dev, _ptr(x), int(x0), nx, ldx, _ptr(taps), taps.numel(), int(up), int(down),
+                _ptr(o), int(n0), ny, ldy, B)
+        return o
+
     def dropout(self, x, mask, p_keep=0.5, scale=2.0, seed=None, offset=0, out=None):
         """y = x * keep * scale. seed None: keep from the uint8 `mask` (the caller's); else Philox4x32-10 bits of
         (seed, offset, index), written into `mask` when given. x None: the mask only. -> y (or mask)."""

@@ -2,7 +2,7 @@
 
     python -m music2dance_amd.phase3.generate -c music2dance_amd/phase3/configs/default.yaml -l <logdir> \
         [--gen-weights PATH] (--audio a.wav [b.wav ...] | --val | --synthetic) [--chunk-frames N] [--seed S] \
-        [--folder DIR] [-d N] [--video]
+        [--folder DIR] [-d N] [--video] [--resampler {fft,poly}]
 
 The reference generates a 30-second sample in phase3/test.py:64-72 (with a broken call) and says its generator
 handles tracks of any length. Frame t of a track reads the audio window track[t hop - left, t hop - left + window)
@@ -19,6 +19,13 @@ seconds of audio, the chunk size, the wall time, the GPU time per chunk (p50 / p
 (seconds of audio per second of wall time). With --video each saved array is also rendered to
 <logdir>/samples/<name>.avi (visualize.frame_to_vid at the config's video_rate), and its track entry gains `video`,
 `render_ms` (device time of the render launches) and `video_s` (wall time of the whole write).
+
+--resampler: how an --audio file that is not at the config's audio_rate gets there. `fft` (the default) converts the
+whole file on the host with scipy.signal.resample before anything is generated, as SequenceDataset.resample_audio does.
+`poly` uploads the file at its own rate and converts it on the device with the polyphase filter of audio.py
+(m2d_resample_poly): in one call for --chunk-frames 0, else chunk by chunk - pushes of chunk_frames * hop * rate_in /
+rate_out source samples go through an audio.StreamResampler into the DanceStream, so the track is never needed whole.
+generation.json records `resampler` and, per track that comes from an --audio file, `source_rate`.
 """
 import argparse
 import json
@@ -28,6 +35,7 @@ import time
 import numpy as np
 import torch
 
+from .. import audio as A
 from .. import kernels, runner
 from ..utils import slice_audio_batch
 from .evaluate import STICK_CHANNELS, build_generator, json_safe, latest_checkpoint
@@ -160,7 +168,18 @@ def parse_args(argv=None):
     ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
     ap.add_argument("--video", action="store_true", help="also render each saved dance to <logdir>/samples/<name>.avi "
                                                          "(300 x 300 stick figures at the config's video_rate)")
+    ap.add_argument("--resampler", choices=("fft", "poly"), default="fft",
+                    help="rate conversion of --audio files: fft = scipy.signal.resample of the whole file on the host, "
+                         "poly = the polyphase filter on the device, streamed with the chunks")
     return ap.parse_args(argv)
+
+
+def load_native(path):
+    """(mono float32 samples of a wav file at its own rate, that rate)"""
+    from scipy.io import wavfile
+    from ..data import _read_wav
+    sr = int(wavfile.read(path, mmap=True)[0])
+    return np.asarray(_read_wav(path), dtype=np.float32), sr
 
 
 def load_track(path, rate):
@@ -176,7 +195,7 @@ def load_track(path, rate):
 
 
 def _tracks(opts, cfg):
-    """-> ([(name, samples)], scaler)"""
+    """-> ([(name, samples, rate of the samples, rate of the wav file they come from or None)], scaler)"""
     from .. import data as D
     ds = cfg["dataset"]
     if opts.synthetic:
@@ -184,11 +203,22 @@ def _tracks(opts, cfg):
         scaler = D.MinMaxScaler().fit(torch.rand(1000, STICK_CHANNELS, generator=g).numpy())
         T = 600
         audio = 0.1 * torch.randn(T * int(ds["audio_rate"] // ds["video_rate"]), generator=g)
-        return [("synthetic", audio.numpy())], scaler
+        return [("synthetic", audio.numpy(), ds["audio_rate"], None)], scaler
     folder = runner.dataset_folder(cfg, opts.folder)
     scaler = D.StickDataset(folder, normalize="minmax").scaler
     if opts.audio:
-        return [(os.path.splitext(os.path.basename(p))[0], load_track(p, ds["audio_rate"])) for p in opts.audio], scaler
+        from scipy.io import wavfile
+        poly = getattr(opts, "resampler", "fft") == "poly"
+        out = []
+        for p in opts.audio:
+            name = os.path.splitext(os.path.basename(p))[0]
+            if poly:
+                samples, sr = load_native(p)
+                out.append((name, samples, sr, sr))
+            else:
+                out.append((name, load_track(p, ds["audio_rate"]), ds["audio_rate"],
+                            int(wavfile.read(p, mmap=True)[0])))
+        return out, scaler
     split = os.path.join(opts.logdir, "trainvaltest_samples.json")
     with open(split) as f:
         val_dirs = json.load(f)["val_samples"]
@@ -197,25 +227,30 @@ def _tracks(opts, cfg):
     missing = [d for d in val_dirs if d not in where]
     if missing:
         raise SystemExit("validation takes not in the dataset: %s" % missing[:5])
-    return [(os.path.basename(os.path.normpath(d)), np.asarray(dataset.musics[where[d]], dtype=np.float32))
-            for d in val_dirs], scaler
+    return [(os.path.basename(os.path.normpath(d)), np.asarray(dataset.musics[where[d]], dtype=np.float32),
+             ds["audio_rate"], None) for d in val_dirs], scaler
 
 
 def _pctl(v, q):
     return float(np.percentile(np.asarray(v, dtype=np.float64), q)) if len(v) else float("nan")
 
 
-def run_track(gen, audio, seed, window, hop, pad, chunk_frames):
+def run_track(gen, audio, seed, window, hop, pad, chunk_frames, rates=None):
     """-> (poses (T, output_size) on the device, timing dict). chunk_frames 0: generate_track; else DanceStream pushes
-    of chunk_frames * hop samples (the track already in device memory), then flush()."""
+    of chunk_frames * hop samples (the track already in device memory), then flush(). rates = (rate_in, rate_out):
+    `audio` is at rate_in and is converted on the device (audio.resample for one call; else every push goes through
+    an audio.StreamResampler, in pieces of chunk_frames * hop * rate_in / rate_out source samples, rounded up)."""
     dev = next(gen.parameters()).device
     audio = audio.to(dev)
+    convert = rates is not None and int(rates[0]) != int(rates[1])
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     events = []
     if chunk_frames <= 0:
         e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         e[0].record()
+        if convert:
+            audio = A.resample(audio, rates[0], rates[1])[0]
         out = generate_track(gen, audio, seed, hop, pad)
         e[1].record()
         events.append(e)
@@ -223,11 +258,18 @@ def run_track(gen, audio, seed, window, hop, pad, chunk_frames):
         stream = DanceStream(gen, window, hop, pad, seed)
         parts = []
         step = chunk_frames * hop
-        pieces = [audio[i:i + step] for i in range(0, audio.shape[0], step)] + [None]
-        for p in pieces:
+        if convert:
+            rs = A.StreamResampler(rates[0], rates[1], 1, dev)
+            step = -(-step * int(rates[0]) // int(rates[1]))
+            feed = lambda p: stream.push(rs.push(p))
+            tail = [lambda: stream.push(rs.flush()), stream.flush]   # the outputs that waited for the future first
+        else:
+            feed, tail = stream.push, [stream.flush]
+        pieces = [audio[i:i + step] for i in range(0, audio.shape[0], step)]
+        for call in [lambda p=p: feed(p.unsqueeze(0)) for p in pieces] + tail:
             e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             e[0].record()
-            rows = stream.push(p.unsqueeze(0)) if p is not None else stream.flush()
+            rows = call()
             e[1].record()
             if rows.shape[1]:
                 events.append(e)
@@ -260,21 +302,24 @@ def generate(opts, cfg, device):
     tracks, scaler = _tracks(opts, cfg)
     outdir = os.path.join(opts.logdir, "samples")
     os.makedirs(outdir, exist_ok=True)
-    res = {"checkpoint": path, "seed": int(opts.seed), "chunk_frames": int(opts.chunk_frames), "tracks": []}
-    for name, samples in tracks:
+    res = {"checkpoint": path, "seed": int(opts.seed), "chunk_frames": int(opts.chunk_frames),
+           "resampler": getattr(opts, "resampler", "fft"), "tracks": []}
+    for name, samples, samples_rate, source_rate in tracks:
         audio = torch.as_tensor(np.ascontiguousarray(samples), dtype=torch.float32)
-        T = n_frames(audio.shape[0], window, hop, pad)
+        T = n_frames(A.out_len(audio.shape[0], *A.ratio(samples_rate, rate)), window, hop, pad)
         if T == 0:
             raise SystemExit("track %s: %d samples hold no frame" % (name, audio.shape[0]))
-        poses, timing = run_track(gen, audio, opts.seed, window, hop, pad, opts.chunk_frames)
+        poses, timing = run_track(gen, audio, opts.seed, window, hop, pad, opts.chunk_frames, (samples_rate, rate))
         assert poses.shape[0] == T, (poses.shape, T)
         arr = scaler.inverse_transform(poses.cpu().numpy().astype(np.float64)).astype(np.float32)
         saved = arr.reshape(T, STICK_CHANNELS // 3, 3)
         np.save(os.path.join(outdir, name + ".npy"), saved)
-        seconds = audio.shape[0] / float(rate)
+        seconds = audio.shape[0] / float(samples_rate)
         res["tracks"].append(dict(name=name, frames=T, seconds=seconds, chunk_frames=int(opts.chunk_frames),
                                   real_time_factor=seconds / timing["wall_s"] if timing["wall_s"] > 0 else None,
                                   **timing))
+        if source_rate is not None:
+            res["tracks"][-1]["source_rate"] = int(source_rate)
         if getattr(opts, "video", False):
             from .. import visualize
             path = os.path.join(outdir, name + ".avi")

@@ -1,0 +1,284 @@
+"""The polyphase resampler on the device (m2d_resample_poly, audio.py, prepare_data, generate --resampler poly):
+parity with scipy.signal.resample_poly in fp64 inside the bound of a P-term fp32 dot product; bit-exact invariance of
+an output under the call's window, first output and absolute position (incl. positions past 2^32); StreamResampler
+against the one-shot call for three chunkings; the argument errors; a raw dataset folder prepared end to end; and a
+dance generated from a 44.1 kHz file streamed at its own rate."""
+import json
+import os
+import shutil
+
+import numpy as np
+import pytest
+import torch
+
+from tests.resample_cases import RAW_TAKES, chunkings, listing, raw_folder
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+WORST = {}
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (up, down) -> (N, B, extra columns of the buffer the rows are cut from: ldx = N + extra)
+CASES = {(160, 441): (44100, 3, 13), (1, 3): (20000, 1, 0), (320, 441): (9001, 1, 0), (2, 1): (5000, 1, 0),
+         (3, 2): (777, 1, 0)}
+_CACHE = {}
+
+
+def note(key, val):
+    WORST[key] = max(WORST.get(key, 0.0), float(val))
+
+
+def K():
+    from music2dance_amd import kernels
+    return kernels.impl()
+
+
+def case(ratio):
+    """(x (B, N) device rows, taps64, taps32 on the device, y (B, ceil(N up / down)) of ONE whole-track call)"""
+    if ratio not in _CACHE:
+        from music2dance_amd import audio as A
+        up, down = ratio
+        N, B, extra = CASES[ratio]
+        g = torch.Generator().manual_seed(1000 + up)
+        x = (0.5 * torch.randn(B, N + extra, generator=g)).to(DEV)[:, :N]
+        r_up, r_down, taps64 = A.design_taps(up, down)
+        assert (r_up, r_down) == ratio
+        taps32 = torch.as_tensor(taps64, dtype=torch.float32).to(DEV)
+        y = K().resample_poly(x, 0, taps32, up, down, 0, A.out_len(N, up, down))
+        torch.cuda.synchronize()
+        _CACHE[ratio] = (x, taps64, taps32, y)
+    return _CACHE[ratio]
+
+
+@pytest.mark.parametrize("ratio", list(CASES), ids=["%dover%d" % r for r in CASES])
+def test_parity_with_scipy_fp64(ratio):
+    from scipy.signal import resample_poly
+    up, down = ratio
+    x, taps64, _, y = case(ratio)
+    N, B, extra = CASES[ratio]
+    assert x.stride(0) == N + extra and tuple(y.shape) == (B, -(-N * up // down))
+    xh = x.cpu().double().numpy()
+    want = resample_poly(xh, up, down, axis=1, window=taps64 / up, padtype="constant")
+    # a P-term fp32 dot product (gamma_P) plus the fp32 rounding of the taps and of the stored result:
+    # |y - y64| <= (P + 3) 2^-24 sum |tap| |x|
+    P = -(-len(taps64) // up)
+    R = resample_poly(np.abs(xh), up, down, axis=1, window=np.abs(taps64) / up, padtype="constant")
+    bound = (P + 3) * 2.0 ** -24 * R
+    err = np.abs(y.cpu().double().numpy() - want)
+    assert want.shape == err.shape
+    pos = bound > 0
+    worst = float((err[pos] / bound[pos]).max())
+    print("resample_poly %d/%d: worst |y - y64| / bound = %.3e" % (up, down, worst))
+    note("resample_poly |y - y64| / ((P + 3) 2^-24 sum|h||x|)  %d/%d" % ratio, worst)
+    assert np.all(err <= bound), worst
+
+
+def test_identity():
+    x = torch.randn(2, 4099, generator=torch.Generator().manual_seed(2)).to(DEV)
+    one = torch.ones(1, device=DEV)
+    y = K().resample_poly(x, 0, one, 1, 1, 0, 4099)
+    assert torch.equal(y, x)
+
+
+def _window(n0, ny, up, down, ntaps, N):
+    """[lo, hi): the samples outputs [n0, n0 + ny) read, cut to the track"""
+    half = (ntaps - 1) // 2
+    lo = max(0, (n0 * down + half - ntaps) // up + 1)
+    hi = min(N, ((n0 + ny - 1) * down + half) // up + 1)
+    return lo, max(lo, hi)
+
+
+@pytest.mark.parametrize("ratio", [(160, 441), (2, 1)], ids=["160over441", "2over1"])
+@pytest.mark.parametrize("split", ["ones", "sevens", "tiles"])
+def test_window_invariance_is_bit_exact(ratio, split):
+    up, down = ratio
+    x, taps64, taps32, whole = case(ratio)
+    N, total = x.shape[1], whole.shape[1]
+    sizes = {"ones": [1] * 40 + [total - 40],
+             "sevens": [7] * (total // 7) + ([total % 7] if total % 7 else []),
+             "tiles": [2047, 1, 2049, total - 4097]}[split]
+    assert sum(sizes) == total and min(sizes) > 0
+    parts, n0, shifted = [], 0, 0
+    for ny in sizes:
+        lo, hi = _window(n0, ny, up, down, len(taps64), N)
+        shifted += lo > 0
+        parts.append(K().resample_poly(x[:, lo:hi], lo, taps32, up, down, n0, ny))
+        n0 += ny
+    assert shifted > 0    # windows declared at a non-zero x0
+    assert torch.equal(torch.cat(parts, 1), whole)
+
+
+def test_positions_past_32_bits():
+    up, down = 160, 441
+    _, _, taps32, _ = case((160, 441))
+    x = torch.randn(2, 400, generator=torch.Generator().manual_seed(4)).to(DEV)
+    m = 2 ** 26
+    near = K().resample_poly(x, 0, taps32, up, down, 5, 50)
+    far = K().resample_poly(x, down * m, taps32, up, down, 5 + up * m, 50)
+    assert (5 + up * m) * down > 2 ** 32
+    assert float(near.abs().max()) > 0 and torch.equal(far, near)
+
+
+def test_strides_past_31_bits_inside_a_tile():
+    """down so large that two neighbouring outputs lie 2^31 filter positions apart (the kernel's 64-bit phase walk):
+    each output has at most one tap, y[n] = taps[phi] x[q] exactly"""
+    up, down, ntaps, ny = 99991, 2 ** 31 - 1, 16383, 64
+    g = torch.Generator().manual_seed(5)
+    taps = torch.randn(ntaps, generator=g)
+    half = (ntaps - 1) // 2
+    nx = ((ny - 1) * down + half) // up + 1
+    x = torch.randn(1, nx, generator=g)
+    want = torch.zeros(1, ny)
+    used = 0
+    for n in range(ny):
+        t = n * down + half
+        if t % up < ntaps:
+            want[0, n] = taps[t % up] * x[0, t // up]
+            used += 1
+    assert used >= 5
+    got = K().resample_poly(x.to(DEV), 0, taps.to(DEV), up, down, 0, ny)
+    assert torch.equal(got.cpu(), want)
+
+
+@pytest.mark.parametrize("name", ["ones", "441s", "mixed"])
+def test_stream_resampler_equals_one_shot(name):
+    from music2dance_amd import audio as A
+    B, N = 2, 30000
+    if "stream" not in _CACHE:
+        x = (0.3 * torch.randn(B, N, generator=torch.Generator().manual_seed(6))).to(DEV)
+        _CACHE["stream"] = (x, A.resample(x, 44100, 16000))
+    x, one = _CACHE["stream"]
+    assert tuple(one.shape) == (B, -(-N * 160 // 441))
+    short = A.StreamResampler(44100, 16000, batch=B, device=DEV)
+    assert tuple(short.push(x[:, :3]).shape) == (B, 0)
+    rs = A.StreamResampler(44100, 16000, batch=B, device=DEV)
+    parts, pos = [], 0
+    for n in chunkings(N)[name]:
+        parts.append(rs.push(x[:, pos:pos + n]))
+        pos += n
+    assert pos == N
+    parts.append(rs.flush())
+    got = torch.cat(parts, 1)
+    assert got.shape == one.shape and torch.equal(got, one)
+
+
+def test_errors():
+    from music2dance_amd._lib import M2dError
+    x = torch.zeros(1, 64, device=DEV)
+    ok = torch.ones(3, device=DEV)
+    assert tuple(K().resample_poly(x, 0, ok, 1, 1, 0, 0).shape) == (1, 0)     # ny = 0: nothing to do
+    with pytest.raises(M2dError):
+        K().resample_poly(x.cpu(), 0, ok, 1, 1, 0, 8)                        # a host tensor
+    with pytest.raises(M2dError, match="odd"):
+        K().resample_poly(x, 0, torch.ones(4, device=DEV), 1, 1, 0, 8)       # even ntaps
+    with pytest.raises(M2dError, match="16384"):
+        K().resample_poly(x, 0, torch.ones(16385, device=DEV), 1, 1, 0, 8)
+    with pytest.raises(M2dError):
+        K().resample_poly(x, 0, ok, 0, 1, 0, 8)                              # up = 0
+    with pytest.raises(M2dError, match="gcd"):
+        K().resample_poly(x, 0, ok, 2, 4, 0, 8)                              # an unreduced ratio
+    with pytest.raises(M2dError):
+        K().resample_poly(x, -1, ok, 1, 1, 0, 8)
+    with pytest.raises(M2dError):
+        K().resample_poly(x, 0, ok, 1, 1, -1, 8)
+    with pytest.raises(M2dError):
+        K().resample_poly(x, 0, ok, 1, 3, 2 ** 62, 8)                        # n down + half would leave 63 bits
+    torch.cuda.synchronize()
+
+
+def test_prepare_data_end_to_end(tmp_path):
+    from scipy.io import wavfile
+    from scipy.signal import resample_poly
+    from music2dance_amd import audio as A
+    from music2dance_amd import prepare_data
+    from music2dance_amd.data import SequenceDataset, _read_wav, retime_sequence
+    folder = raw_folder(str(tmp_path / "raw"))
+    fresh = shutil.copytree(folder, str(tmp_path / "fresh"))
+    rep = prepare_data.main([folder, "--waltz-factor", "0.5"])
+    assert all(t["audio"].startswith("written") for t in rep["takes"])
+    cfg = {"audio_rate": 16000, "video_rate": 25, "seq_length": 1, "feat_size": 0.2}
+    ds = SequenceDataset(folder, cfg, withaudio=True)
+    assert len(ds) == len(RAW_TAKES) and all(len(m) == 32000 for m in ds.musics)
+    for n, (style, rate, fmt) in RAW_TAKES.items():
+        d = os.path.join(folder, "DANCE_%s_%d" % (style, n))
+        sr, pcm = wavfile.read(os.path.join(d, "resampled_audio_extract.wav"))
+        assert sr == 16000 and pcm.dtype == np.int16 and pcm.ndim == 1
+        if rate == 16000:
+            assert np.array_equal(pcm, wavfile.read(os.path.join(d, "audio_extract.wav"))[1])
+            continue
+        up, down, taps64 = A.design_taps(16000, rate)
+        x = _read_wav(os.path.join(d, "audio_extract.wav"))
+        assert x.dtype == np.float32 and x.ndim == 1
+        y64 = resample_poly(x.astype(np.float64), up, down, window=taps64 / up, padtype="constant")
+        want = np.clip(np.rint(32768.0 * y64), -32768, 32767)
+        off = np.abs(pcm.astype(np.float64) - want)
+        flips = float((off != 0).mean())
+        print("prepare_data %s (%d Hz %s): %.4f %% of the PCM samples one LSB off the fp64 rounding"
+              % (style, rate, fmt, 100 * flips))
+        note("prepare_data fraction of PCM samples 1 LSB off fp64 (%d Hz %s)" % (rate, fmt), flips)
+        assert off.max() <= 1 and flips <= 0.01
+    w = os.path.join(folder, "DANCE_W_4")
+    with open(os.path.join(w, "skeletons.json")) as f:
+        src = json.load(f)
+    with open(os.path.join(w, "new_skeletons.json")) as f:
+        new = json.load(f)
+    n_new = int(round(len(src["skeletons"]) / 2.0))
+    assert new["length"] == n_new == len(new["skeletons"]) == len(new["center"])
+    assert np.array_equal(np.asarray(new["skeletons"]), retime_sequence(src["skeletons"], n_new))
+    assert np.array_equal(np.asarray(new["center"]), retime_sequence(src["center"], n_new))
+    # a second run finds everything in place
+    before = listing(folder)
+    rep = prepare_data.main([folder, "--waltz-factor", "0.5"])
+    assert listing(folder) == before
+    assert all(t["audio"] == "skipped: exists" for t in rep["takes"])
+    assert {t["take"]: t for t in rep["takes"]}["DANCE_W_4"]["waltz"] == "skipped: exists"
+    # --dry-run on a fresh copy writes nothing
+    before = listing(fresh)
+    prepare_data.main([fresh, "--waltz-factor", "0.5", "--dry-run"])
+    assert listing(fresh) == before
+
+
+def test_generate_with_the_polyphase_resampler(tmp_path):
+    from scipy.io import wavfile
+    from music2dance_amd import runner
+    from music2dance_amd.data import StickDataset, write_synthetic_dataset
+    from music2dance_amd.phase3 import generate as G
+    from music2dance_amd.phase3.evaluate import build_generator
+    cfg_path = os.path.join(ROOT, "music2dance_amd", "phase3", "configs", "default.yaml")
+    cfg = runner.load_config(cfg_path)
+    data = write_synthetic_dataset(str(tmp_path / "data"), n_takes=4, seconds=2)
+    torch.manual_seed(0)
+    weights = str(tmp_path / "gen.pt")
+    torch.save(build_generator(cfg, "cpu").state_dict(), weights)
+    N = 3 * 44100
+    pcm = np.clip(np.random.RandomState(8).randn(N) * 3000.0, -32767, 32767).astype(np.int16)
+    wav = str(tmp_path / "song.wav")
+    wavfile.write(wav, 44100, pcm)
+    T = G.n_frames(-(-N * 160 // 441), 3200, 640, 2560)
+    assert T == 75
+    scaler = StickDataset(data, normalize="minmax").scaler
+
+    def run(name, *extra):
+        logdir = str(tmp_path / name)
+        res = G.main(["-c", cfg_path, "-l", logdir, "--gen-weights", weights, "--audio", wav, "--folder", data,
+                      "--seed", "3"] + list(extra))
+        path = os.path.join(logdir, "samples", "song.npy")
+        with open(os.path.join(logdir, "samples", "generation.json")) as f:
+            assert json.load(f) == json.loads(json.dumps(res))
+        return res, np.load(path), open(path, "rb").read()
+
+    res, streamed, _ = run("poly25", "--resampler", "poly", "--chunk-frames", "25")
+    assert res["resampler"] == "poly" and res["tracks"][0]["source_rate"] == 44100
+    assert res["tracks"][0]["frames"] == T and res["tracks"][0]["seconds"] == pytest.approx(3.0)
+    res, whole, _ = run("poly0", "--resampler", "poly", "--chunk-frames", "0")
+    assert streamed.shape == whole.shape == (T, 23, 3) and np.isfinite(whole).all()
+    # the generator's own (MinMax-scaled) outputs, under the criterion of test_gpu_dance_stream's stream-vs-one-shot test
+    a, b = (scaler.transform(v.reshape(T, 69).astype(np.float64)) for v in (streamed, whole))
+    d = float(np.abs(a - b).max())
+    note("generate --resampler poly |streamed - one-shot| (scaled poses)", d)
+    assert d < 1e-4, d
+    # fft is the default, and stays what it was: the same bytes with and without the flag
+    res, default, default_bytes = run("default", "--chunk-frames", "25")
+    assert res["resampler"] == "fft" and res["tracks"][0]["source_rate"] == 44100
+    res, _, fft_bytes = run("fft", "--resampler", "fft", "--chunk-frames", "25")
+    assert default.shape[1:] == (23, 3) and fft_bytes == default_bytes
