@@ -1,15 +1,19 @@
-"""Shared scaffolding of the three train scripts: YAML config, run folders, optional
-TensorBoard, checkpoints with the reference's file names, synthetic batches.
+"""The training driver of the four GAN train scripts: their flags, run set-up, loaders and the epoch loop (`train`),
+with YAML config, run folders, optional TensorBoard and checkpoints under the reference's file names.
 
 The scripts run on `--synthetic` batches of the dataset's shapes, or - through music2dance_amd.data, the
 reference's dataset pipeline (utils.py:15-194, phase3/train.py:114-162) - on a Music-to-Dance-Motion-Synthesis
 folder (`folder:` of the YAML, or `--folder`).
 """
+import argparse
+import collections
 import datetime
 import os
 
 import torch
 import yaml
+
+from . import dp
 
 
 def load_config(path):
@@ -180,3 +184,140 @@ def staged(tensors, device, derive=None):
     for t in _tensors(out):
         t.record_stream(cur)
     return out, ready
+
+
+# ------------------------------------------------------------------------------------------- the training driver
+def train_parser(batch_size=True, graphs=None, framework=None):
+    """The flags every train script takes. Opt-in: `--batch-size`; `graphs`, the help text of `--graphs` (with it comes
+    `--no-graphs`); `framework`, the help text of `-f`."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("-c", "--config", type=str, help="choose config file")
+    ap.add_argument("-d", "--device", type=int, help="choose gpu id")
+    ap.add_argument("-n", "--name", type=str, help="name experiment")
+    if framework:
+        ap.add_argument("-f", "--framework", type=str, default="wgangp", help=framework)
+    ap.add_argument("--synthetic", action="store_true", help="random batches of the dataset's shapes")
+    ap.add_argument("--folder", type=str, default=None, help="dataset folder (overrides the YAML's `folder:`)")
+    ap.add_argument("--iterations", type=int, default=None, help="stop after this many loop bodies")
+    if batch_size:
+        ap.add_argument("--batch-size", type=int, default=None, help="override batch_size (per GPU)")
+    ap.add_argument("--log-every", type=int, default=1)
+    ap.add_argument("--no-run-dir", action="store_true")
+    ap.add_argument("--sync-bn", action="store_true", help="data parallel: BatchNorm statistics over the global batch")
+    ap.add_argument("--host-loader", action="store_true",
+                    help="fetch and collate batches on the host (torch DataLoader, as the reference does) instead of "
+                         "gathering them from the HBM-resident dataset; same batches either way")
+    if graphs:
+        ap.add_argument("--graphs", action="store_true", help=graphs)
+        ap.add_argument("--no-graphs", action="store_true", help="keep the eager launch loop on a single GPU too")
+    return ap
+
+
+Run = collections.namedtuple("Run", "rank world device cfg opts")
+
+
+def start(opts):
+    rank, world, local = dp.init_from_env()
+    return Run(rank, world, pick_device(local if world > 1 else opts.device), load_config(opts.config), opts)
+
+
+def run_dir(run):
+    return make_run_dir(run.opts.name, enabled=(run.rank == 0 and not run.opts.no_run_dir))
+
+
+def sequence_shape(run):
+    """(stick_length, batch_size) of a sequence phase: poses per sequence from the YAML, `--batch-size` over the YAML's."""
+    ds = run.cfg["dataset"]
+    return int(ds["seq_length"] * ds["video_rate"]), run.opts.batch_size or run.cfg["batch_size"]
+
+
+def subset_loader(run, dataset, batch_size, collate_fn=None):
+    """Full batches of a random subset of the first `num_train` items: gathered from the HBM-resident dataset on a HIP
+    device, by a torch DataLoader on the host with `--host-loader` (or without a device)."""
+    from torch.utils.data import DataLoader, SubsetRandomSampler
+    from . import data as D
+    sampler = SubsetRandomSampler(range(min(run.cfg["num_train"], len(dataset))))
+    if run.device.type == "cuda" and not run.opts.host_loader:
+        return D.ResidentLoader(dataset, batch_size, sampler, run.device, drop_last=True)
+    return DataLoader(dataset, batch_size=batch_size, drop_last=True, sampler=sampler, collate_fn=collate_fn)
+
+
+def sequence_dataset(run, withaudio):
+    """MinMax-scaled pose sequences (the scaler fitted on all still poses), random crops."""
+    from . import data as D
+    folder = dataset_folder(run.cfg, run.opts.folder)
+    print("Loading sticks and sequences datasets...")
+    sticks = D.StickDataset(folder, normalize="minmax")
+    return D.SequenceDataset(folder, run.cfg["dataset"], dance_types=run.cfg["dance_types"], scaler=sticks.scaler,
+                             withaudio=withaudio)
+
+
+def pose_sequence_loader(run, batch_size):
+    """phase2/train.py:66-70,115-116: pose sequences without audio under a random subset sampler; also the
+    dataset's stick_length."""
+    from . import data as D
+    dataset = sequence_dataset(run, withaudio=False)
+    return subset_loader(run, dataset, batch_size, lambda b: D.collate_fn(b, withaudio=False)), dataset.stick_length
+
+
+def synthetic_seeds(run, epoch):
+    """Seeds of one epoch's synthetic batches, distinct per batch and rank. (The number of batches comes from the YAML's
+    batch size whatever `--batch-size` says.)"""
+    n = max(run.cfg["num_train"] // run.cfg["batch_size"], 1)
+    return (1 + (epoch * n + b) * run.world + run.rank for b in range(n))
+
+
+def graphs_on(run):
+    """Captured HIP graphs by default on one GPU; data parallel the exchange stays outside the graphs, so only on request."""
+    return run.device.type == "cuda" and (run.opts.graphs or (run.world == 1 and not run.opts.no_graphs))
+
+
+def train(run, logdir, engine, batches, scalars, checkpoints, train_mode=("gen",), architectures=True, started=None,
+          epoch_end=None):
+    """The loop of a train script, from the built engine to the closing print.
+    batches(epoch):       the epoch's batches, each (train_step's positional arguments, event after which they are
+                          complete or None); every step is `engine.train_step(*args, inputs_ready=event)`, so an
+                          engine run by this driver takes `inputs_ready` (None: nothing to wait for)
+    scalars(out):         what to log of a train_step's result, tag -> value, or None on an iteration that logs nothing
+    checkpoints(epoch):   [(module name, file name), ...] due after that epoch (needs a run directory)
+    train_mode:           the engine's modules put into train mode at the top of every epoch
+    architectures:        write model_gen.txt / model_critic.txt into the run directory
+    started(log):         optional, once before the first epoch
+    epoch_end(epoch, log, done): optional, after every epoch's batches - also those of the epoch in which `--iterations`
+                          was reached (done), which ends the run right after: no checkpoint follows it."""
+    log = ScalarLog(logdir, run.opts.log_every)
+    if architectures:
+        dump_architectures(logdir, engine.gen, engine.critic)
+    if started is not None:
+        started(log)
+    modules = [getattr(engine, name) for name in train_mode]
+    stop = run.opts.iterations
+    settle_garbage_collector()
+    print("Start training..")
+    done = False
+    for epoch in range(run.cfg["num_epochs"]):
+        for m in modules:
+            m.train()
+        for args, ready in batches(epoch):
+            out = engine.train_step(*args, inputs_ready=ready)
+            it = engine.total_iterations
+            values = scalars(out)
+            if values is not None:
+                log.scalars(values, it)
+            if stop is not None and it >= stop:
+                done = True
+                break
+        if epoch_end is not None:
+            epoch_end(epoch, log, done)
+        if done:
+            break
+        due = checkpoints(epoch) if logdir is not None else ()
+        if any(name == "critic" for name, _ in due):
+            engine.flush()  # a deferred (data-parallel) critic step must be in the checkpoint
+        for name, file in due:
+            save_state(getattr(engine, name), logdir + "/models/" + file)
+    engine.flush()
+    log.flush()
+    if run.rank == 0:
+        print("done: {} iterations, last {}".format(engine.total_iterations,
+                                                    {k: float(v) for k, v in engine.last.items()}))

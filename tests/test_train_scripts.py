@@ -122,6 +122,102 @@ def test_phase1_train_script_runs(dev, tmp_path, monkeypatch):
     assert eng.total_iterations == 5 and "loss_gen" in eng.last
 
 
+# ------------------------------------------------------------------------------ the shared driver (runner.train)
+_COMMON = {"-h", "--help", "-c", "--config", "-d", "--device", "-n", "--name", "--synthetic", "--folder", "--iterations",
+           "--log-every", "--no-run-dir", "--sync-bn", "--host-loader"}
+_GRAPHS = {"--graphs", "--no-graphs"}
+_CLI = {"phase1.train_wgan_gp": _COMMON | _GRAPHS,
+        "phase2.train": _COMMON | _GRAPHS | {"--batch-size", "-f", "--framework"},
+        "phase2.train_conditional": _COMMON | {"--batch-size", "-f", "--framework"},
+        "phase3.train": _COMMON | {"--batch-size", "--val-batches"}}
+
+
+def _script(name):
+    import importlib
+    return importlib.import_module("music2dance_amd." + name)
+
+
+@pytest.mark.parametrize("name", sorted(_CLI))
+def test_train_script_flags(name):
+    assert set(_script(name).parser()._option_string_actions) == _CLI[name]
+
+
+def test_train_scripts_refuse_flags_they_never_had(tmp_path):
+    cfg = _cfg(tmp_path, "phase1/configs/b2l50s32.yaml")
+    with pytest.raises(SystemExit):
+        _script("phase3.train").main(["-c", cfg, "-d", "0", "-n", "x", "--synthetic", "--no-run-dir", "--graphs"])
+    with pytest.raises(SystemExit):
+        _script("phase1.train_wgan_gp").main(["-c", cfg, "-d", "0", "-n", "x", "--synthetic", "--no-run-dir",
+                                              "--batch-size", "4"])
+
+
+_EPOCHS = (1, 5, 99, 100, 500, 1000, 1100, 4999, 5000, 10000)
+_P2_DUE = {5000: [("gen", "gpgen_5000.pt"), ("critic", "gpcritic_5000.pt")],
+           10000: [("gen", "gpgen_10000.pt"), ("critic", "gpcritic_10000.pt")]}
+_DUE = {"phase1.train_wgan_gp": {5: [("gen", "gen_5.pt"), ("critic", "critic_5.pt")],
+                                 100: [("gen", "gen_100.pt"), ("critic", "critic_100.pt")],
+                                 500: [("gen", "gen_500.pt"), ("critic", "critic_500.pt")],
+                                 1000: [("gen", "gen_1000.pt"), ("critic", "critic_1000.pt")],
+                                 1100: [("gen", "gen_1100.pt"), ("critic", "critic_1100.pt")],
+                                 5000: [("gen", "gen_5000.pt"), ("critic", "critic_5000.pt")],
+                                 10000: [("gen", "gen_10000.pt"), ("critic", "critic_10000.pt")]},
+        "phase2.train": _P2_DUE,
+        "phase2.train_conditional": _P2_DUE,
+        "phase3.train": {100: [("gen", "gpgen_100.pt")], 500: [("gen", "gpgen_500.pt")], 1000: [("gen", "gpgen_1000.pt")],
+                         5000: _P2_DUE[5000], 10000: _P2_DUE[10000]}}
+
+
+@pytest.mark.parametrize("name", sorted(_DUE))
+def test_checkpoint_schedules(name):
+    """What runner.train saves after epoch N - 1, as (module of the engine, file under models/)."""
+    schedule = _script(name).checkpoints
+    assert {n: list(schedule(n - 1)) for n in _EPOCHS} == {n: _DUE[name].get(n, []) for n in _EPOCHS}
+
+
+def test_checkpoints_through_the_loop(dev, tmp_path, monkeypatch):
+    """Six one-batch epochs of phase 1 with a run directory: the schedule's files and no others, written when they
+    were due (the epoch-5 state, not the final one)."""
+    from music2dance_amd.phase1 import train_wgan_gp as T
+    from music2dance_amd.phase1.archis.residual import Discriminator, Generator
+    monkeypatch.chdir(tmp_path)
+    path = _cfg(tmp_path, "phase1/configs/b2l50s32.yaml", batch_size=8, num_train=8, num_epochs=6)
+    eng = T.main(["-c", path, "-d", "0", "-n", "ck", "--synthetic"])
+    assert eng.total_iterations == 6
+    models = glob.glob(str(tmp_path / "runs" / "*_ck"))[0] + "/models"
+    assert sorted(os.listdir(models)) == ["critic_5.pt", "gen_5.pt"]
+    cfg = yaml.safe_load(open(path))
+    gen = Generator(cfg["latent_vector_size"], cfg["size"], cfg["output_size"], cfg["nblocks_gen"])
+    critic = Discriminator(cfg["output_size"], cfg["size"], cfg["nblocks_critic"])
+    gen.load_state_dict(torch.load(models + "/gen_5.pt", map_location="cpu"), strict=True)
+    critic.load_state_dict(torch.load(models + "/critic_5.pt", map_location="cpu"), strict=True)
+    # epoch 6 is a critic iteration (n_critic_steps = 5): it moves the critic's parameters and, through the generator
+    # forward, the generator's BatchNorm buffers
+    final = {k: v.cpu() for k, v in eng.gen.state_dict().items()}
+    assert not all(torch.equal(v, final[k]) for k, v in gen.state_dict().items())
+    final = {k: v.detach().cpu() for k, v in eng.critic.named_parameters()}
+    assert not all(torch.equal(v, final[k]) for k, v in critic.named_parameters())
+
+
+def test_iterations_stop_inside_an_epoch(dev, tmp_path, monkeypatch):
+    """`--iterations 3` with two batches per epoch stops inside epoch 2: phase 3 still validates that epoch (and leaves
+    the generator in train mode), nobody trains on."""
+    from music2dance_amd.phase2 import train as T2
+    from music2dance_amd.phase3 import train as T3
+    monkeypatch.chdir(tmp_path)
+    seen = []
+    orig = runner.ScalarLog.scalars
+    monkeypatch.setattr(runner.ScalarLog, "scalars", lambda self, d, step, **kw: (seen.append((sorted(d), step)),
+                                                                                 orig(self, d, step, **kw))[1])
+    small = dict(batch_size=2, num_train=4, num_epochs=3, n_critic_steps=2)
+    argv = ["-d", "0", "-n", "s", "--synthetic", "--no-run-dir", "--iterations", "3"]
+    eng = T3.main(["-c", _cfg(tmp_path, "phase3/configs/ablated.yaml", **small)] + argv)
+    assert eng.total_iterations == 3 and eng.gen.training
+    assert np.isfinite(float(T3.LAST_LOG.last["l1_loss_val"]))
+    assert [step for tags, step in seen if tags == ["l1_loss_val"]] == [2, 3]
+    eng = T2.main(["-c", _cfg(tmp_path, "phase2/configs/default.yaml", **small), "-f", "wgangp"] + argv)
+    assert eng.total_iterations == 3
+
+
 # ------------------------------------------------------------------------------ dataset path (SURVEY.md 8(f) row 4)
 def test_train_scripts_run_on_a_dataset_folder(dev, tmp_path, monkeypatch):
     """Without --synthetic the scripts go through music2dance_amd.data (the reference's StickDataset /
