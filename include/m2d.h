@@ -450,6 +450,51 @@ int m2d_render_sticks(const float* poses, long n_frames, int height, int width, 
 int m2d_resample_poly(const float* x, long long x0, int nx, long long ldx, const float* taps, int ntaps, int up,
                       int down, float* y, long long n0, int ny, long long ldy, int B, void* stream);
 
+/* ---- beat alignment of a dance with its music (metrics.py; no counterpart in the reference) --
+ * STFT band energies. n_fft: a power of two in [256, 2048]; nbins = n_fft / 2 + 1; w[n] = 0.5 - 0.5 cos(2 pi n / n_fft)
+ * (periodic Hann). Row b of x (B rows, ldx floats apart) holds samples [0, S) of a track, every other sample is zero.
+ * Frame t (any t >= 0, 64-bit) starts at sample s_t = t hop + hop / 2 - n_fft / 2 (integer divisions). For frames
+ * t = frame0 .. frame0 + T - 1 and bands 0 .. nb - 1 (nb <= 128):
+ *   re[k] = sum_n table[0][k][n] x[s_t + n], im[k] = sum_n table[1][k][n] x[s_t + n], P[k] = re^2 + im^2 (k < nbins),
+ *   E[(b T + t - frame0) nb + band] = sum_k bands[band nbins + k] P[k]
+ * with table (2, nbins, n_fft) = [w[n] cos(2 pi ((n k) mod n_fft) / n_fft); -w[n] sin(the same)], made on the HOST in
+ * fp64 and rounded to fp32 (the device never takes the cosine of a large argument). The kernel reads the table as the
+ * packed image pack_basis makes of it (image_elems floats, 16-byte aligned; image_elems is 0 for a bad n_fft): the
+ * sine row of bin 0 is identically zero and is not kept, its place carries the cosine row of bin n_fft / 2. All sums
+ * are fp32 (v_mfma_f32_32x32x2_f32 for both contractions) in a fixed order: the value of a frame is a bit-level pure
+ * function of t, the samples of its window, the table and the bands, whatever frame0, T, B, ldx and the launch's
+ * tiling - a track may be processed in chunks of frames. Frames that lie past the track are exactly zero. No atomics,
+ * no workspace; neither the windows (B, T, n_fft) nor the spectrum (B, T, 2 nbins) is ever written.
+ * M2D_ERR_ARG (nothing launched): n_fft not such a power of two; nb outside [1, 128]; hop or B <= 0; T, S or frame0
+ * < 0; ldx < S; a null or misaligned pointer; (frame0 + T) hop near 2^63. T == 0: nothing to do. */
+size_t m2d_stft_image_elems(int n_fft);
+int m2d_stft_pack_basis(const float* table, int n_fft, float* image, void* stream);
+int m2d_stft_bands(const float* x, long long ldx, int S, int B, long long frame0, int T, int hop, int n_fft,
+                   const float* image, const float* bands, int nb, float* E, void* stream);
+/* onset strength of band energies E (B, T, nb), contiguous: o[b T] = 0 and, for t >= 1,
+ *   o[b T + t] = (1 / nb) sum_band max(0, log1pf(gamma E[t][band]) - log1pf(gamma E[t - 1][band])),
+ * one fp32 accumulator over ascending bands. gamma >= 0. One pass, no workspace. */
+int m2d_onset_flux(const float* E, int B, int T, int nb, float gamma, float* o, void* stream);
+/* mean joint speed of poses (B, T, J, 3), contiguous, T >= 2: for t >= 1
+ *   v[b T + t] = (1 / J) sum_j sqrtf(dx^2 + dy^2 + dz^2), d = p[t][j] - p[t - 1][j],
+ * one fp32 accumulator over ascending j; v[b T] = v[b T + 1] (the same operations). */
+int m2d_motion_speed(const float* poses, int B, int T, int J, float* v, void* stream);
+/* Beat alignment of onset strength o and motion speed v, both (B, T) contiguous, row by row (one workgroup a row):
+ *   smoothing g(c, sigma)[t] = sum_j w_j c[t + j] / sum_j w_j over j in [-R, R] with 0 <= t + j < T, R = ceil(3 sigma),
+ *     w_j = exp(-j^2 / (2 sigma^2)): summed in fp64 in ascending j and rounded to fp32 once;
+ *   music events M: t in [1, T - 2] with s[t] > s[t - 1], s[t] >= s[t + 1] and s[t] > mean_t s, s = g(o, sigma_onset);
+ *   motion events K: t in [1, T - 2] with u[t] < u[t - 1] and u[t] <= u[t + 1], u = g(v, sigma_speed);
+ *   scores[4 b + 0] = mean over k in K of expf(-d^2 / (2 sigma_align^2)), d = min over m in M of |k - m|
+ *     (two directional scans), [4 b + 1] the same with K and M exchanged, [4 b + 2] = |K|, [4 b + 3] = |M|;
+ *     both scores are NaN when K or M is empty (always for T < 3).
+ * Optional outputs (NULL: not wanted): motion_events, music_events (B, T) bytes 0 / 1; onset_smooth, speed_smooth
+ * (B, T) fp32. Every sum has a fixed order, no atomics: bit-stable. M2D_ERR_ARG (nothing launched): B <= 0, T < 0,
+ * T > max_frames (16384), a sigma <= 0 or a radius ceil(3 sigma) > 64, a null pointer. */
+int m2d_beat_align_max_frames(void);
+int m2d_beat_align(const float* onset, const float* speed, int B, int T, double sigma_onset, double sigma_speed,
+                   double sigma_align, float* scores, unsigned char* motion_events, unsigned char* music_events,
+                   float* onset_smooth, float* speed_smooth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

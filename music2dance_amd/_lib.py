@@ -121,6 +121,13 @@ SIGNATURES = {
     "m2d_render_sticks": (_I, [_F, _L, _I, _I, _F, _F]),
     "m2d_resample_poly": (_I, [_F, _c.c_longlong, _I, _c.c_longlong, _F, _I, _I, _I, _F, _c.c_longlong, _I, _c.c_longlong,
                                 _I, _F]),
+    "m2d_stft_image_elems": (_S, [_I]),
+    "m2d_stft_pack_basis": (_I, [_F, _I, _F, _F]),
+    "m2d_stft_bands": (_I, [_F, _c.c_longlong, _I, _I, _c.c_longlong, _I, _I, _I, _F, _F, _I, _F, _F]),
+    "m2d_onset_flux": (_I, [_F, _I, _I, _I, _f, _F, _F]),
+    "m2d_motion_speed": (_I, [_F, _I, _I, _I, _F, _F]),
+    "m2d_beat_align_max_frames": (_I, []),
+    "m2d_beat_align": (_I, [_F, _F, _I, _I, _c.c_double, _c.c_double, _c.c_double, _F, _F, _F, _F, _F, _F]),
 }
 
 _lib = None

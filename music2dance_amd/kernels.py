@@ -1131,6 +1131,89 @@ class HipKernels:
                 _ptr(o), int(n0), ny, ldy, B)
         return o
 
+    # ---------------------------------------------------------------- beat alignment (metrics.py)
+    def stft_pack_basis(self, table):
+        """table (2, n_fft / 2 + 1, n_fft) fp32, the windowed DFT basis made on the host -> the image m2d_stft_bands
+        reads (m2d_stft_pack_basis); kept like the weight images inside a weight_cache() scope (metrics.stft_basis
+        keeps one per (n_fft, device) besides)"""
+        dev = _chk(table)
+        n_fft = table.shape[-1] if table.dim() == 3 else 0
+        elems = _lib.lib().m2d_stft_image_elems(int(n_fft))
+        if elems == 0 or tuple(table.shape) != (2, n_fft // 2 + 1, n_fft):
+            raise _lib.M2dError("stft_pack_basis: a (2, n_fft / 2 + 1, n_fft) table with n_fft a power of two in "
+                                "[256, 2048] expected, got %s" % (tuple(table.shape),))
+
+        def build():
+            image = torch.empty((elems,), dtype=torch.float32, device=dev)
+            _launch("m2d_stft_pack_basis", dev, _ptr(table), int(n_fft), _ptr(image))
+            return image
+
+        return self._image(table, "stft", build)
+
+    def stft_bands(self, x, n_frames, hop, n_fft, image, bands, frame0=0):
+        """Band energies E (B, n_frames, nb) of STFT frames frame0 .. of audio rows x (B, S) (rows may be cut from a
+        wider buffer); image: stft_pack_basis's of this n_fft; bands (nb, n_fft / 2 + 1) fp32 (m2d_stft_bands)"""
+        ldx = self._chk_audio_rows(x, "x")
+        dev = _chk(image, bands)
+        if dev != x.device:
+            raise _lib.M2dError("stft_bands: the basis image and the bands must be on %s" % x.device)
+        B, S = x.shape
+        T, hop, n_fft = int(n_frames), int(hop), int(n_fft)
+        if bands.dim() != 2 or n_fft < 2 or bands.shape[1] != n_fft // 2 + 1:
+            raise _lib.M2dError("stft_bands: bands must be (nb, n_fft / 2 + 1), got %s" % (tuple(bands.shape),))
+        if image.numel() != _lib.lib().m2d_stft_image_elems(n_fft):
+            raise _lib.M2dError("stft_bands: n_fft must be a power of two in [256, 2048] and the image packed for it "
+                                "(got n_fft = %d, an image of %d floats)" % (n_fft, image.numel()))
+        nb = bands.shape[0]
+        if T < 0 or B == 0:
+            raise _lib.M2dError("stft_bands: n_frames < 0 or no rows")
+        E = torch.empty((B, T, nb), dtype=torch.float32, device=dev)
+        _launch("m2d_stft_bands", dev, _ptr(x), ldx, S, B, int(frame0), T, hop, n_fft, _ptr(image), _ptr(bands), nb,
+                _ptr(E))
+        return E
+
+    def onset_flux(self, E, gamma=1.0):
+        """E (B, T, nb) -> onset strength (B, T) (m2d_onset_flux)"""
+        dev = _chk(E)
+        if E.dim() != 3 or E.shape[0] == 0 or E.shape[2] == 0:
+            raise _lib.M2dError("onset_flux: band energies (B, T, nb) expected, got %s" % (tuple(E.shape),))
+        B, T, nb = E.shape
+        o = torch.empty((B, T), dtype=torch.float32, device=dev)
+        _launch("m2d_onset_flux", dev, _ptr(E), B, T, nb, float(gamma), _ptr(o))
+        return o
+
+    def motion_speed(self, poses):
+        """poses (B, T, J, 3), T >= 2 -> mean joint speed (B, T) (m2d_motion_speed)"""
+        dev = _chk(poses)
+        if poses.dim() != 4 or poses.shape[3] != 3:
+            raise _lib.M2dError("motion_speed: poses (B, T, J, 3) expected, got %s" % (tuple(poses.shape),))
+        B, T, J, _ = poses.shape
+        v = torch.empty((B, T), dtype=torch.float32, device=dev)
+        _launch("m2d_motion_speed", dev, _ptr(poses), B, T, J, _ptr(v))
+        return v
+
+    def beat_align(self, onset, speed, sigma_onset=1.0, sigma_speed=2.0, sigma_align=2.0, return_events=False):
+        """onset, speed (B, T) -> scores (B, 4) = [beat_align, beat_cover, |K|, |M|] (m2d_beat_align); with
+        return_events also (motion events, music events (B, T) uint8, smoothed onset, smoothed speed (B, T))"""
+        dev = _chk(onset, speed)
+        if onset.dim() != 2 or onset.shape != speed.shape or onset.shape[0] == 0:
+            raise _lib.M2dError("beat_align: onset and speed must both be (B, T), got %s and %s"
+                                % (tuple(onset.shape), tuple(speed.shape)))
+        B, T = onset.shape
+        limit = _lib.lib().m2d_beat_align_max_frames()
+        if T > limit:
+            raise _lib.M2dError("beat_align: %d frames a row, the kernel takes at most %d (score the track in "
+                                "sections)" % (T, limit))
+        scores = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        extra = (None,) * 4
+        if return_events:
+            extra = (torch.empty((B, T), dtype=torch.uint8, device=dev), torch.empty((B, T), dtype=torch.uint8, device=dev),
+                     torch.empty((B, T), dtype=torch.float32, device=dev),
+                     torch.empty((B, T), dtype=torch.float32, device=dev))
+        _launch("m2d_beat_align", dev, _ptr(onset), _ptr(speed), B, T, float(sigma_onset), float(sigma_speed),
+                float(sigma_align), _ptr(scores), *[_ptr(t) for t in extra])
+        return (scores,) + extra if return_events else scores
+
     def dropout(self, x, mask, p_keep=0.5, scale=2.0, seed=None, offset=0, out=None):
         """y = x * keep * scale. seed None: keep from the uint8 `mask` (the caller's); else Philox4x32-10 bits of
         (seed, offset, index), written into `mask` when given. x None: the mask only. -> y (or mask)."""

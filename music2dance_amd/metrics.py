@@ -1,0 +1,134 @@
+"""Music-dance beat alignment on the device (include/m2d.h "beat alignment").
+
+Jerkiness and style agreement (phase3.evaluate) never look at the music. This module asks whether the kinematic beats
+of a dance - local minima of the body's speed - fall on musical onsets, as the beat-alignment scores of AIST++ and
+"Dancing to Music" do:
+
+    audio -> STFT band energies (m2d_stft_bands: the DFT on fp32 MFMA, the mel projection fused)
+          -> onset strength (m2d_onset_flux: log-compressed, rectified spectral flux)
+    poses -> mean joint speed (m2d_motion_speed)
+    both  -> smoothing, events, nearest-event distances, beat_align and beat_cover (m2d_beat_align)
+
+Pose frame t belongs to samples [t hop, (t + 1) hop); STFT frame t is centred on the middle of that interval. Device
+tensors in, device tensors out, no host synchronisation inside. The window, the mel bands, the smoothing widths and
+gamma are conventions of this project (the reference has no such metric); all are parameters.
+"""
+import numpy as np
+import torch
+
+from . import _lib, kernels
+from .audio import _rows
+
+N_JOINTS = 23
+_BASIS = {}   # (n_fft, device) -> (fp32 table on the device, its packed image)
+_BANDS = {}   # (n_bands, n_fft, rate, device) -> fp32 mel bands on the device
+
+
+def mel_bands(n_bands=40, n_fft=1024, rate=16000):
+    """float64 (n_bands, n_fft / 2 + 1): HTK-mel triangles of peak 1; n_bands + 2 points equally spaced in
+    mel(f) = 2595 log10(1 + f / 700) from mel(0) to mel(rate / 2) are the corners f_0 .. f_{n_bands + 1};
+    bands[b, k] = max(0, min((F_k - f_b) / (f_{b+1} - f_b), (f_{b+2} - F_k) / (f_{b+2} - f_{b+1}))), F_k = k rate / n_fft"""
+    n_bands, n_fft = int(n_bands), int(n_fft)
+    mel_hi = 2595.0 * np.log10(1.0 + (rate / 2.0) / 700.0)
+    f = 700.0 * (10.0 ** (np.linspace(0.0, mel_hi, n_bands + 2) / 2595.0) - 1.0)
+    F = np.arange(n_fft // 2 + 1, dtype=np.float64) * rate / n_fft
+    up = (F[None, :] - f[:-2, None]) / (f[1:-1] - f[:-2])[:, None]
+    down = (f[2:, None] - F[None, :]) / (f[2:] - f[1:-1])[:, None]
+    return np.maximum(0.0, np.minimum(up, down))
+
+
+def stft_table(n_fft):
+    """The host half of stft_basis: float32 (2, n_fft / 2 + 1, n_fft), [w[n] cos(a); -w[n] sin(a)] with
+    a = 2 pi ((n k) mod n_fft) / n_fft and w the periodic Hann window, evaluated in fp64 and rounded once"""
+    n_fft = int(n_fft)
+    if n_fft < 256 or n_fft > 2048 or n_fft & (n_fft - 1):
+        raise ValueError("n_fft must be a power of two in [256, 2048], got %d" % n_fft)
+    n = np.arange(n_fft, dtype=np.int64)
+    k = np.arange(n_fft // 2 + 1, dtype=np.int64)
+    a = 2.0 * np.pi * ((k[:, None] * n[None, :]) % n_fft).astype(np.float64) / n_fft
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * n.astype(np.float64) / n_fft)
+    return np.stack((w[None, :] * np.cos(a), -w[None, :] * np.sin(a))).astype(np.float32)
+
+
+def stft_basis(n_fft, device):
+    """The packed basis image m2d_stft_bands reads, made once per (n_fft, device)"""
+    device = torch.device(device)
+    key = (int(n_fft), str(device))
+    ent = _BASIS.get(key)
+    if ent is None:
+        if key[0] < 256 or key[0] > 2048 or key[0] & (key[0] - 1):
+            raise _lib.M2dError("stft_basis: n_fft must be a power of two in [256, 2048], got %d" % key[0])
+        table = torch.from_numpy(stft_table(n_fft)).to(device)
+        ent = _BASIS[key] = (table, kernels.impl().stft_pack_basis(table))
+    return ent[1]
+
+
+def _device_bands(bands, n_fft, rate, device):
+    if bands is None:
+        key = (40, int(n_fft), int(rate), str(device))
+        b = _BANDS.get(key)
+        if b is None:
+            b = _BANDS[key] = torch.as_tensor(mel_bands(40, n_fft, rate), dtype=torch.float32).to(device)
+        return b
+    b = torch.as_tensor(bands).detach().to(device=device, dtype=torch.float32).contiguous()
+    if b.dim() != 2 or b.shape[1] != int(n_fft) // 2 + 1:
+        raise ValueError("bands: (nb, n_fft / 2 + 1) expected, got %s" % (tuple(b.shape),))
+    return b
+
+
+def band_energies(audio, n_frames, hop, n_fft=1024, bands=None, rate=16000, frame0=0):
+    """audio (N,) or (B, N) fp32 on the device -> E (B, n_frames, nb): band energies of STFT frames frame0 ..
+    frame0 + n_frames - 1 (frame t is centred on t hop + hop / 2; zeros outside the track). Bit-identical however
+    the frames of a track are cut into calls. bands None: mel_bands(40, n_fft, rate)."""
+    x = _rows(audio)
+    return kernels.impl().stft_bands(x, int(n_frames), int(hop), int(n_fft), stft_basis(n_fft, x.device),
+                                     _device_bands(bands, n_fft, rate, x.device), int(frame0))
+
+
+def onset_strength(audio, n_frames, hop, n_fft=1024, bands=None, rate=16000, gamma=1.0):
+    """-> o (B, n_frames): o[0] = 0, o[t] = mean over bands of max(0, L[t] - L[t - 1]), L = log1p(gamma E)"""
+    return kernels.impl().onset_flux(band_energies(audio, n_frames, hop, n_fft, bands, rate), gamma)
+
+
+def _pose_rows(poses):
+    p = torch.as_tensor(poses)
+    if p.dim() >= 2 and p.shape[-1] != 3:      # (..., T, 3 J)
+        if p.shape[-1] % 3:
+            raise ValueError("poses: (B, T, J, 3) or (B, T, 3 J) expected, got %s" % (tuple(p.shape),))
+        p = p.reshape(p.shape[:-1] + (p.shape[-1] // 3, 3))
+    if p.dim() == 3:
+        p = p.unsqueeze(0)
+    if p.dim() != 4:
+        raise ValueError("poses: (B, T, J, 3) or (B, T, 3 J) expected, got %s" % (tuple(p.shape),))
+    return p.contiguous()
+
+
+def motion_speed(poses):
+    """poses (B, T, J, 3) or (B, T, 3 J) (one dance: (T, J, 3) or (T, 3 J)) in world units, T >= 2 -> v (B, T):
+    v[t] = mean over joints of |p[t] - p[t - 1]|, v[0] = v[1]"""
+    return kernels.impl().motion_speed(_pose_rows(poses))
+
+
+def beat_alignment(onset, speed, sigma_onset=1.0, sigma_speed=2.0, sigma_align=2.0, return_events=False):
+    """onset, speed (B, T) -> {'align', 'cover', 'n_motion', 'n_music'} (B,) device tensors; align = mean over
+    kinematic beats of exp(-d^2 / (2 sigma_align^2)), d the distance (frames) to the nearest musical onset; cover the
+    same over the onsets; both NaN where a row has no kinematic beat or no onset. return_events: also
+    'motion_events', 'music_events' (B, T) uint8 and 'onset_smooth', 'speed_smooth' (B, T)."""
+    out = kernels.impl().beat_align(onset, speed, sigma_onset, sigma_speed, sigma_align, return_events)
+    scores = out[0] if return_events else out
+    res = {"align": scores[:, 0], "cover": scores[:, 1], "n_motion": scores[:, 2], "n_music": scores[:, 3]}
+    if return_events:
+        res.update(motion_events=out[1], music_events=out[2], onset_smooth=out[3], speed_smooth=out[4])
+    return res
+
+
+def beat_scores(audio, poses, hop, rate=16000, n_fft=1024, bands=None, gamma=1.0, **kw):
+    """audio (B, N) at `rate` Hz and the dances poses (B, T, J, 3) / (B, T, 3 J) it accompanies, `hop` samples a pose
+    frame -> beat_alignment(...) of the onset strength of the T frames against the motion speed; **kw: its sigmas
+    and return_events"""
+    p = _pose_rows(poses)
+    x = _rows(audio)
+    if x.shape[0] != p.shape[0]:
+        raise ValueError("beat_scores: %d audio rows for %d dances" % (x.shape[0], p.shape[0]))
+    onset = onset_strength(x, p.shape[1], hop, n_fft, bands, rate, gamma)
+    return beat_alignment(onset, motion_speed(p), **kw)

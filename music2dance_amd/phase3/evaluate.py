@@ -1,7 +1,7 @@
 """Score a trained phase-3 generator as the reference's phase3/test.py:76-140 does, on the HIP path.
 
     python -m music2dance_amd.phase3.evaluate -c music2dance_amd/phase3/configs/default.yaml -l <logdir> \
-        --classifier logs/type2/weights.pt [--gen-weights PATH] [--repeats 20] [--synthetic]
+        --classifier logs/type2/weights.pt [--gen-weights PATH] [--repeats 20] [--synthetic] [--beat-align]
 
 1. Jerkiness (losses.jerkiness) of every real validation take and of the dance generated from its music, on
    inverse-MinMax-scaled poses: mean and unbiased standard deviation of each.
@@ -15,6 +15,12 @@ random crop per draw, as the reference's loader makes); all draws go through ONE
 BatchNorm keeps the rows independent, so only the order of the noise draws differs from the reference's batch-1 loop).
 The generator checkpoint defaults to the latest <logdir>/models/gpgen_*.pt. Writes <logdir>/evaluation.json, strict
 JSON: an undefined value (a confusion row without samples, the spread of a single sequence) is `null`.
+
+--beat-align adds the music-dance beat alignment (metrics.beat_scores) of every real draw and of
+its generated counterpart against the draw's own audio row: `beat_align_{real,fake}_{mean,std}`,
+`beat_cover_{real,fake}_{mean,std}` over the rows whose score is defined (a row without a kinematic beat or without an
+onset has none) and `beat_defined_{real,fake}`, the number of such rows. Without the flag evaluation.json is what it
+was.
 """
 import argparse
 import glob
@@ -44,6 +50,8 @@ def parse_args(argv=None):
     ap.add_argument("--synthetic", action="store_true", help="random poses / audio / styles of the dataset's shapes")
     ap.add_argument("--folder", type=str, default=None, help="dataset folder (overrides the YAML's `folder:`)")
     ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
+    ap.add_argument("--beat-align", action="store_true", help="also score the beat alignment of the real and the "
+                                                              "generated dances with their music")
     return ap.parse_args(argv)
 
 
@@ -76,14 +84,44 @@ def jerk_stats(values):
     return float(v.mean()), (float(v.std(ddof=1)) if v.size > 1 else float("nan"))
 
 
-def summary(real_jerk, fake_jerk, real_pred, fake_pred, n_classes=N_STYLES):
+def beat_stats(align, cover, tag):
+    """The beat-alignment keys of one side (`tag` = real / fake): mean and unbiased standard deviation of beat_align
+    and beat_cover over the rows where the score is defined (both are NaN together), and how many rows those are"""
+    align = np.asarray(align, dtype=np.float64).reshape(-1)
+    cover = np.asarray(cover, dtype=np.float64).reshape(-1)
+    ok = np.isfinite(align) & np.isfinite(cover)
+    out = {"beat_defined_%s" % tag: int(ok.sum())}
+    for name, v in (("align", align[ok]), ("cover", cover[ok])):
+        out["beat_%s_%s_mean" % (name, tag)] = float(v.mean()) if v.size else float("nan")
+        out["beat_%s_%s_std" % (name, tag)] = float(v.std(ddof=1)) if v.size > 1 else float("nan")
+    return out
+
+
+def beat_rows(audio, real_i, fake_i, hop, rate):
+    """-> {'real': (align, cover), 'fake': (align, cover)}, numpy (N,) each: metrics.beat_scores of the inverse-scaled
+    dances (N, T, 69) against the audio rows (N, S) they were drawn with. A drawn take's audio row starts at its first
+    pose frame (SequenceDataset.sample_batch), so pose frame t belongs to samples [t hop, (t + 1) hop) of the row."""
+    from .. import metrics
+    out = {}
+    for tag, poses in (("real", real_i), ("fake", fake_i)):
+        s = metrics.beat_scores(audio, poses.contiguous(), hop, rate=rate)
+        out[tag] = (s["align"].cpu().numpy(), s["cover"].cpu().numpy())
+    return out
+
+
+def summary(real_jerk, fake_jerk, real_pred, fake_pred, n_classes=N_STYLES, beat=None):
+    """beat: beat_rows' result, or None (the keys of --beat-align are then absent)"""
     cm, counts = confusion(real_pred, fake_pred, n_classes)
     rm, rs = jerk_stats(real_jerk)
     fm, fs = jerk_stats(fake_jerk)
     total = int(counts.sum())
-    return {"jerk_real_mean": rm, "jerk_real_std": rs, "jerk_fake_mean": fm, "jerk_fake_std": fs,
-            "confusion": cm.tolist(), "style_agreement": float(np.trace(counts)) / total if total else float("nan"),
-            "n_sequences": total}
+    res = {"jerk_real_mean": rm, "jerk_real_std": rs, "jerk_fake_mean": fm, "jerk_fake_std": fs,
+           "confusion": cm.tolist(), "style_agreement": float(np.trace(counts)) / total if total else float("nan"),
+           "n_sequences": total}
+    if beat is not None:
+        for tag in ("real", "fake"):
+            res.update(beat_stats(beat[tag][0], beat[tag][1], tag))
+    return res
 
 
 def json_safe(v):
@@ -172,8 +210,11 @@ def evaluate(opts, cfg, device):
     # style classification of every real take and its generated counterpart (phase3/test.py:107-140)
     _, real_pred = ops.cross_entropy_pred(classifier(real.permute(0, 2, 1).contiguous()), labels)
     _, fake_pred = ops.cross_entropy_pred(classifier(fake.permute(0, 2, 1).contiguous()), labels)
+    beat = None
+    if getattr(opts, "beat_align", False):
+        beat = beat_rows(audio.contiguous(), real_i, fake_i, hop, int(cfg["dataset"]["audio_rate"]))
     return summary(real_jerk.cpu().numpy(), fake_jerk.cpu().numpy(), real_pred.cpu().numpy(),
-                   fake_pred.cpu().numpy())
+                   fake_pred.cpu().numpy(), beat=beat)
 
 
 def main(argv=None):

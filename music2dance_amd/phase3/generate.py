@@ -2,7 +2,7 @@
 
     python -m music2dance_amd.phase3.generate -c music2dance_amd/phase3/configs/default.yaml -l <logdir> \
         [--gen-weights PATH] (--audio a.wav [b.wav ...] | --val | --synthetic) [--chunk-frames N] [--seed S] \
-        [--folder DIR] [-d N] [--video] [--resampler {fft,poly}]
+        [--folder DIR] [-d N] [--video] [--resampler {fft,poly}] [--beat-align]
 
 The reference generates a 30-second sample in phase3/test.py:64-72 (with a broken call) and says its generator
 handles tracks of any length. Frame t of a track reads the audio window track[t hop - left, t hop - left + window)
@@ -26,6 +26,11 @@ whole file on the host with scipy.signal.resample before anything is generated, 
 (m2d_resample_poly): in one call for --chunk-frames 0, else chunk by chunk - pushes of chunk_frames * hop * rate_in /
 rate_out source samples go through an audio.StreamResampler into the DanceStream, so the track is never needed whole.
 generation.json records `resampler` and, per track that comes from an --audio file, `source_rate`.
+
+--beat-align: each track entry gains `beat_align`, `beat_cover`, `beat_motion_events` and `beat_music_events`, the beat
+alignment (metrics.beat_scores) of the saved poses with the track at the model's rate - with
+--resampler poly the device's own conversion of the file (the streamed pieces, concatenated, equal it bit for bit).
+Tracks longer than the alignment kernel's row limit fail loudly.
 """
 import argparse
 import json
@@ -171,6 +176,8 @@ def parse_args(argv=None):
     ap.add_argument("--resampler", choices=("fft", "poly"), default="fft",
                     help="rate conversion of --audio files: fft = scipy.signal.resample of the whole file on the host, "
                          "poly = the polyphase filter on the device, streamed with the chunks")
+    ap.add_argument("--beat-align", action="store_true", help="score each dance's beat alignment with its track "
+                                                              "(beat_* keys of generation.json)")
     return ap.parse_args(argv)
 
 
@@ -235,11 +242,13 @@ def _pctl(v, q):
     return float(np.percentile(np.asarray(v, dtype=np.float64), q)) if len(v) else float("nan")
 
 
-def run_track(gen, audio, seed, window, hop, pad, chunk_frames, rates=None):
+def run_track(gen, audio, seed, window, hop, pad, chunk_frames, rates=None, track_out=None):
     """-> (poses (T, output_size) on the device, timing dict). chunk_frames 0: generate_track; else DanceStream pushes
     of chunk_frames * hop samples (the track already in device memory), then flush(). rates = (rate_in, rate_out):
     `audio` is at rate_in and is converted on the device (audio.resample for one call; else every push goes through
-    an audio.StreamResampler, in pieces of chunk_frames * hop * rate_in / rate_out source samples, rounded up)."""
+    an audio.StreamResampler, in pieces of chunk_frames * hop * rate_in / rate_out source samples, rounded up).
+    track_out: a list that receives the track at rate_out as the generator saw it, (S,) on the device (the converted
+    pieces of a streamed run, concatenated)."""
     dev = next(gen.parameters()).device
     audio = audio.to(dev)
     convert = rates is not None and int(rates[0]) != int(rates[1])
@@ -251,6 +260,8 @@ def run_track(gen, audio, seed, window, hop, pad, chunk_frames, rates=None):
         e[0].record()
         if convert:
             audio = A.resample(audio, rates[0], rates[1])[0]
+        if track_out is not None:
+            track_out.append(audio)
         out = generate_track(gen, audio, seed, hop, pad)
         e[1].record()
         events.append(e)
@@ -261,10 +272,19 @@ def run_track(gen, audio, seed, window, hop, pad, chunk_frames, rates=None):
         if convert:
             rs = A.StreamResampler(rates[0], rates[1], 1, dev)
             step = -(-step * int(rates[0]) // int(rates[1]))
-            feed = lambda p: stream.push(rs.push(p))
-            tail = [lambda: stream.push(rs.flush()), stream.flush]   # the outputs that waited for the future first
+            converted = []
+
+            def keep(y):
+                if track_out is not None:
+                    converted.append(y[0])
+                return y
+
+            feed = lambda p: stream.push(keep(rs.push(p)))
+            tail = [lambda: stream.push(keep(rs.flush())), stream.flush]   # the outputs that waited for the future first
         else:
             feed, tail = stream.push, [stream.flush]
+            if track_out is not None:
+                track_out.append(audio)
         pieces = [audio[i:i + step] for i in range(0, audio.shape[0], step)]
         for call in [lambda p=p: feed(p.unsqueeze(0)) for p in pieces] + tail:
             e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -275,6 +295,8 @@ def run_track(gen, audio, seed, window, hop, pad, chunk_frames, rates=None):
                 events.append(e)
             parts.append(rows[0])
         out = torch.cat(parts, 0)
+        if convert and track_out is not None:
+            track_out.append(torch.cat(converted, 0))
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
     kernels.HipKernels.check_async_errors()
@@ -309,7 +331,10 @@ def generate(opts, cfg, device):
         T = n_frames(A.out_len(audio.shape[0], *A.ratio(samples_rate, rate)), window, hop, pad)
         if T == 0:
             raise SystemExit("track %s: %d samples hold no frame" % (name, audio.shape[0]))
-        poses, timing = run_track(gen, audio, opts.seed, window, hop, pad, opts.chunk_frames, (samples_rate, rate))
+        beat = getattr(opts, "beat_align", False)
+        heard = [] if beat else None
+        poses, timing = run_track(gen, audio, opts.seed, window, hop, pad, opts.chunk_frames, (samples_rate, rate),
+                                  heard)
         assert poses.shape[0] == T, (poses.shape, T)
         arr = scaler.inverse_transform(poses.cpu().numpy().astype(np.float64)).astype(np.float32)
         saved = arr.reshape(T, STICK_CHANNELS // 3, 3)
@@ -320,6 +345,11 @@ def generate(opts, cfg, device):
                                   **timing))
         if source_rate is not None:
             res["tracks"][-1]["source_rate"] = int(source_rate)
+        if beat:
+            from .. import metrics
+            s = metrics.beat_scores(heard[0].contiguous(), torch.from_numpy(saved).to(heard[0].device), hop, rate=rate)
+            res["tracks"][-1].update(beat_align=float(s["align"][0]), beat_cover=float(s["cover"][0]),
+                                     beat_motion_events=int(s["n_motion"][0]), beat_music_events=int(s["n_music"][0]))
         if getattr(opts, "video", False):
             from .. import visualize
             path = os.path.join(outdir, name + ".avi")
