@@ -477,9 +477,7 @@ __global__ void __launch_bounds__(256) m2d_bn_apply_kernel(const BnApplyArgs a, 
       const float xh = (xv[j] - mu[j]) * is[j];
       const float z = g[j] * xh + bt[j];
       if (!a.backward) {
-        float y = z;
-        if (a.act == 1) y = z > 0.f ? z : 0.f;
-        else if (a.act == 2) y = z > 0.f ? z : z * a.slope;
+        float y = m2d_act(z, a.act, a.slope);
         if (a.residual) y += rv[j];
         ov[j] = y;
       } else {
@@ -529,10 +527,7 @@ __global__ void __launch_bounds__(256) m2d_bn_upsample2_flat_kernel(const BnAppl
     auto norm = [&](float x, float gg, float bb, float mm, float ii) {
       const float xh = (x - mm) * ii;
       const float z = gg * xh + bb;
-      float y = z;
-      if (a.act == 1) y = z > 0.f ? z : 0.f;
-      else if (a.act == 2) y = z > 0.f ? z : z * a.slope;
-      return y;
+      return m2d_act(z, a.act, a.slope);
     };
     const float2 raw = *reinterpret_cast<const float2*>(xs + g);
     const float n0 = norm(raw.x, g0, b0, m0, i0), n1 = norm(raw.y, g1, b1, m1, i1);
@@ -580,10 +575,7 @@ __global__ void __launch_bounds__(256) m2d_bn_upsample2_rows_kernel(const BnAppl
   auto norm = [&](float x) {
     const float xh = (x - mm) * ii;
     const float z = gg * xh + bb;
-    float y = z;
-    if (a.act == 1) y = z > 0.f ? z : 0.f;
-    else if (a.act == 2) y = z > 0.f ? z : z * a.slope;
-    return y;
+    return m2d_act(z, a.act, a.slope);
   };
 #pragma unroll 2
   for (int r = r0; r < B; r += rstep) {

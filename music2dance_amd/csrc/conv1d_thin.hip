@@ -39,6 +39,15 @@ typedef float thin_f32x16 __attribute__((ext_vector_type(16)));
 typedef float thin_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned thin_u32x4 __attribute__((ext_vector_type(4)));
 
+// m2d_act_sel (m2d_common.h) behind plain tests of the launch-uniform `act`, with `act` a constant in each arm: the compiler
+// then moves the tests out of the unrolled epilogue. The forward kernel sits just under its 128-VGPR ceiling, and the
+// branch-free form with a run-time `act` spills 8 registers there.
+__device__ __forceinline__ float thin_act(float v, int act, float slope) {
+  if (act == 0) return v;
+  if (act == 1) return m2d_act_sel(v, 1, 0.f);
+  return m2d_act_sel(v, 2, slope);
+}
+
 template <int KS, int S, bool MASKED>
 __global__ void __launch_bounds__(256) thin_bwd_weight_mfma_kernel(const ThinArgs a) {
   constexpr int LD = 65;             // [co][l] image, odd stride: fragment reads (lanes along co) are conflict-free
@@ -448,7 +457,6 @@ thin_fwd_mfma_kernel(const ThinArgs a, int tiles_per_row, int total_tiles) {
   float bv[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) bv[i] = a.bias ? a.bias[crow + 8 * i] : 0.f;
-  const float act_s = a.act == 0 ? 1.f : (a.act == 1 ? 0.f : a.slope);   // max(v, 0) + s min(v, 0)
   const float ms = a.mask_slope;
   double st1[4] = {0.0, 0.0, 0.0, 0.0}, st2[4] = {0.0, 0.0, 0.0, 0.0};   // statistics of this wave's tiles (a lane's share)
   const unsigned row_bytes = (unsigned)a.Lout * 4u;
@@ -506,10 +514,7 @@ thin_fwd_mfma_kernel(const ThinArgs a, int tiles_per_row, int total_tiles) {
         const thin_f32x4 q = *reinterpret_cast<const thin_f32x4*>(im + co * LDP + 4 * cq);
         thin_f32x4 v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float t = q[j] + bv[i];
-          v[j] = fmaxf(t, 0.f) + act_s * fminf(t, 0.f);
-        }
+        for (int j = 0; j < 4; ++j) v[j] = thin_act(q[j] + bv[i], a.act, a.slope);
         if (a.mask) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] *= mk[i][j] > 0.f ? 1.f : ms;
@@ -533,7 +538,7 @@ thin_fwd_mfma_kernel(const ThinArgs a, int tiles_per_row, int total_tiles) {
         float v[4] = {q.x + b_, q.y + b_, q.z + b_, q.w + b_};
         const size_t o = ((size_t)n * 32 + co) * a.Lout + p0 + 4 * cq;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f) + act_s * fminf(v[j], 0.f);
+        for (int j = 0; j < 4; ++j) v[j] = thin_act(v[j], a.act, a.slope);
         if (whole && valign == 4) {
           if (a.mask) {
             const float4 m = *reinterpret_cast<const float4*>(a.mask + o);
@@ -709,7 +714,6 @@ __global__ void __launch_bounds__(512) thin_long_fwd_kernel(const ThinArgs a, in
   float bv[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) bv[i] = a.bias ? a.bias[crow + 8 * i] : 0.f;
-  const float act_s = a.act == 0 ? 1.f : (a.act == 1 ? 0.f : a.slope);
   const unsigned row_bytes = (unsigned)a.Lout * 4u;
   const unsigned sample_bytes = 32u * row_bytes;
 
@@ -795,10 +799,7 @@ __global__ void __launch_bounds__(512) thin_long_fwd_kernel(const ThinArgs a, in
       const thin_f32x4 q = *reinterpret_cast<const thin_f32x4*>(im + co * LDP + 4 * cq);
       thin_f32x4 v;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float t = q[j] + bv[i];
-        v[j] = fmaxf(t, 0.f) + act_s * fminf(t, 0.f);
-      }
+      for (int j = 0; j < 4; ++j) v[j] = thin_act(q[j] + bv[i], a.act, a.slope);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(thin_u32x4, v), ro, (int)(eo + (unsigned)(8 * i) * row_bytes), 0, 0);
       // statistics: a lane's four values of channel row crow + 8 i, summed over ALL the wave's tiles in registers; the
       // eight lanes of a row meet once, after the last tile (one partial per (wave, channel): the tile -> wave assignment

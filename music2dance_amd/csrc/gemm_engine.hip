@@ -310,8 +310,7 @@ __device__ __forceinline__ float m2d_epilogue(const M2dOutMap& o, float v, int r
   const int maddr = (o.mask_wrap && addr >= (int)o.mask_wrap) ? addr - (int)o.mask_wrap : addr;
   if (o.bias_mode == 1) v += o.bias[row];
   else if (o.bias_mode == 2) v += o.bias[col];
-  if (o.act == 1) v = v > 0.f ? v : 0.f;
-  else if (o.act == 2) v = v > 0.f ? v : v * o.slope;
+  v = m2d_act(v, o.act, o.slope);
   if (o.mask_last) {
     if (o.residual) v += o.residual[addr];
     if (o.mask) v *= (o.mask[maddr] > 0.f ? 1.f : o.mask_slope);
@@ -517,10 +516,9 @@ __device__ __forceinline__ void m2d_tile_epilogue(const M2dGemmParams& p, const 
       // ---- fast pass: no residual, plain row map (and, one element per lane: no statistics, no redirect column in
       // this tile). A dozen instructions per element, no branch: the general pass below spends ~150 on its uniform
       // feature tests, and a lane has 64 elements (20 us per workgroup on a plain GEMM tile, measured).
-      //   activation: max(x, 0) + s min(x, 0) with s = 1 / 0 / slope (none / ReLU / leaky) - equal to the selects up to
-      //   the sign of a zero; mask: one bit per element, fetched in one burst per tile
+      //   activation: m2d_act (m2d_common.h), the selects of the general pass - NaN and +-inf come out as torch gives them;
+      //   mask: one bit per element, fetched in one burst per tile
       {
-        const float act_s = act == 0 ? 1.f : (act == 1 ? 0.f : O.slope);
         bool fast = !has_res && m_div <= 0;
         // (one element per lane: no redirect column in this tile; statistics only in the form that re-reads the image in
         // 16-byte pieces below - no output mask, no position window)
@@ -540,10 +538,10 @@ __device__ __forceinline__ void m2d_tile_epilogue(const M2dGemmParams& p, const 
                 for (int it = 0; it < 4; ++it) {
                   const int rl = rl0 + 8 * it;
                   float4 x = m2d_ld4(wl + jj * 1024 + rl * 32 + c4);
-                  x.x = colb + 0 < N ? fmaxf(x.x, 0.f) + act_s * fminf(x.x, 0.f) : 0.f;
-                  x.y = colb + 1 < N ? fmaxf(x.y, 0.f) + act_s * fminf(x.y, 0.f) : 0.f;
-                  x.z = colb + 2 < N ? fmaxf(x.z, 0.f) + act_s * fminf(x.z, 0.f) : 0.f;
-                  x.w = colb + 3 < N ? fmaxf(x.w, 0.f) + act_s * fminf(x.w, 0.f) : 0.f;
+                  x.x = colb + 0 < N ? m2d_act_sel(x.x, act, O.slope) : 0.f;
+                  x.y = colb + 1 < N ? m2d_act_sel(x.y, act, O.slope) : 0.f;
+                  x.z = colb + 2 < N ? m2d_act_sel(x.z, act, O.slope) : 0.f;
+                  x.w = colb + 3 < N ? m2d_act_sel(x.w, act, O.slope) : 0.f;
                   float a1 = (x.x + x.y) + (x.z + x.w);
                   float a2 = (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w);
 #pragma unroll
@@ -599,10 +597,10 @@ __device__ __forceinline__ void m2d_tile_epilogue(const M2dGemmParams& p, const 
               if constexpr (WIDE) {
                 float4 x = m2d_ld4(img + it * (RS * 32));
                 const unsigned kb = keep >> (4 * it);
-                x.x = (fmaxf(x.x, 0.f) + act_s * fminf(x.x, 0.f)) * ((kb & 1u) ? 1.f : ms);
-                x.y = (fmaxf(x.y, 0.f) + act_s * fminf(x.y, 0.f)) * ((kb & 2u) ? 1.f : ms);
-                x.z = (fmaxf(x.z, 0.f) + act_s * fminf(x.z, 0.f)) * ((kb & 4u) ? 1.f : ms);
-                x.w = (fmaxf(x.w, 0.f) + act_s * fminf(x.w, 0.f)) * ((kb & 8u) ? 1.f : ms);
+                x.x = m2d_act(x.x, act, O.slope) * ((kb & 1u) ? 1.f : ms);
+                x.y = m2d_act(x.y, act, O.slope) * ((kb & 2u) ? 1.f : ms);
+                x.z = m2d_act(x.z, act, O.slope) * ((kb & 4u) ? 1.f : ms);
+                x.w = m2d_act(x.w, act, O.slope) * ((kb & 8u) ? 1.f : ms);
                 m2d_bstore4(rso, voff, x);
                 if (stats) {  // this tile's 32 columns of the row: the 8 lanes that share it
                   float a1 = ok ? (x.x + x.y) + (x.z + x.w) : 0.f;
@@ -620,7 +618,7 @@ __device__ __forceinline__ void m2d_tile_epilogue(const M2dGemmParams& p, const 
                 }
               } else {
                 float x = img[it * (RS * 32)];
-                x = (fmaxf(x, 0.f) + act_s * fminf(x, 0.f)) * (((keep >> it) & 1u) ? 1.f : ms);
+                x = m2d_act_sel(x, act, O.slope) * (((keep >> it) & 1u) ? 1.f : ms);
                 m2d_bstore1(rso, voff, x);
               }
             }
@@ -691,12 +689,8 @@ __device__ __forceinline__ void m2d_tile_epilogue(const M2dGemmParams& p, const 
           float a1 = 0.f, a2 = 0.f;
           if constexpr (WIDE) {
             float4 x = m2d_ld4(wl + jj * 1024 + rl * 32 + c4);
-            if (act == 1) {
-              x.x = x.x > 0.f ? x.x : 0.f; x.y = x.y > 0.f ? x.y : 0.f; x.z = x.z > 0.f ? x.z : 0.f; x.w = x.w > 0.f ? x.w : 0.f;
-            } else if (act == 2) {
-              x.x = x.x > 0.f ? x.x : x.x * O.slope; x.y = x.y > 0.f ? x.y : x.y * O.slope;
-              x.z = x.z > 0.f ? x.z : x.z * O.slope; x.w = x.w > 0.f ? x.w : x.w * O.slope;
-            }
+            x.x = m2d_act(x.x, act, O.slope); x.y = m2d_act(x.y, act, O.slope);
+            x.z = m2d_act(x.z, act, O.slope); x.w = m2d_act(x.w, act, O.slope);
             if (has_res && O.mask_last) {  // (a load and its use inside ONE uniform branch: launches without a residual carry no wait)
               const float4 r4 = m2d_bload4(M2D_RS(O.residual), voff);
               x.x += r4.x; x.y += r4.y; x.z += r4.z; x.w += r4.w;
@@ -727,8 +721,7 @@ __device__ __forceinline__ void m2d_tile_epilogue(const M2dGemmParams& p, const 
           } else {
             float x = wl[jj * 1024 + rl * 32 + l31];
             if (redirect && (NT > 1 && jj ? red_t[NT - 1] : red_t[0]) && row < p.M) O.col_out[row] = x;  // raw: a bias gradient
-            if (act == 1) x = x > 0.f ? x : 0.f;
-            else if (act == 2) x = x > 0.f ? x : x * O.slope;
+            x = m2d_act_sel(x, act, O.slope);
             if (has_res && O.mask_last) x += m2d_bload(M2D_RS(O.residual), voff, 0);
             x *= ((keep >> qq) & 1u) ? 1.f : ms;
             if (has_res && !O.mask_last) {
@@ -1047,8 +1040,7 @@ __device__ __forceinline__ void m2d_tile_epilogue_quad(const M2dGemmParams& p, c
         for (int e = 0; e < 4; ++e) {
           float x = acc[i][j][4 * g + e];
           if (O.bias_mode == 1) x += O.bias[row + e];
-          if (O.act == 1) x = x > 0.f ? x : 0.f;
-          else if (O.act == 2) x = x > 0.f ? x : x * O.slope;
+          x = m2d_act(x, O.act, O.slope);
           v[e] = x;
         }
         if (whole) {

@@ -59,5 +59,25 @@ typedef struct M2dAdamItem {
   int cout, cin, ks, reserved;
 } M2dAdamItem;
 
+// The fused activation of every epilogue (act: 0 none, 1 ReLU, 2 leaky with `slope`). It gives what
+// torch.nn.functional gives on the same fp32 value: NaN -> NaN and +inf -> +inf for every act, -inf -> 0 under ReLU and
+// -inf otherwise (non-finite values pass through). One select on `v < 0` - a NaN compares false and is
+// handed on untouched - over v times 1 / 0 / slope, formed with v_mul_legacy_f32, whose 0 x anything is 0: -inf x 0 is 0
+// under ReLU, not NaN, and the multiplicand is never a NaN (it is < 0). No fmax / fmin: on gfx9 they return the operand
+// that is not a NaN. `act` is uniform per launch, so the factor is a scalar formed once: three VALU per element.
+extern "C" __device__ float m2d_fmul_legacy(float, float) __asm("llvm.amdgcn.fmul.legacy");
+
+__device__ __forceinline__ float m2d_act(float v, int act, float slope) {
+  const float s = act == 0 ? 1.f : (act == 1 ? 0.f : slope);
+  return v < 0.f ? m2d_fmul_legacy(v, s) : v;
+}
+
+// The same function without the multiply under ReLU, as two selects: for the one-element engine epilogue and
+// conv1d_thin.hip, whose kernels sit at a register ceiling and spill SGPRs or VGPRs with the form above.
+__device__ __forceinline__ float m2d_act_sel(float v, int act, float slope) {
+  const float neg = act == 1 ? 0.f : v * slope;
+  return (act != 0 && v < 0.f) ? neg : v;
+}
+
 static inline int m2d_ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long m2d_ceil_div64(long long a, long long b) { return (a + b - 1) / b; }

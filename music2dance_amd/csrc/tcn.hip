@@ -385,7 +385,6 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
   }
   __syncthreads();
   {
-    const float act_s = p.act == 0 ? 1.f : (p.act == 1 ? 0.f : p.slope);
     const float ms = p.out_mask_slope;
     const bool has_mask = p.out_mask != nullptr;
 #pragma unroll
@@ -395,7 +394,7 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
                     *reinterpret_cast<const tcn_f32x4*>(smem + 128 * LDE + erow[i]);
       if (p.bias) v += p.bias[(tid + 512 * i) / PPR];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f) + act_s * fminf(v[j], 0.f);
+      for (int j = 0; j < 4; ++j) v[j] = m2d_act(v[j], p.act, p.slope);
       tcn_f32x4 mk = {1.f, 1.f, 1.f, 1.f};
       if (has_mask) {
 #pragma unroll
