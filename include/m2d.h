@@ -44,11 +44,9 @@ int m2d_prof_begin(void);
 int m2d_prof_end(double* out, int n_out /* >= 20 */);
 /* per-launch CSV "family,tag,d0,d1,d2,ms,flops,bytes" of the current session; call before m2d_prof_end */
 int m2d_prof_dump(char* buf, int cap);
-/* GEMM-engine launch plans (tile height, split-K factor) come from a cost model; with M2D_AUTOTUNE=1
- * the best few are timed once per operand shape, on the caller's operands, and the fastest is cached.
- * Number of shapes timed so far: */
-int m2d_plan_cache_size(void);
-/* Round 5: which cost model ranks the GEMM engine's launch plans (tile height, split-K factor). 4 (default): the
+/* GEMM-engine launch plans (tile height, split-K factor) come from a cost model: nothing is timed, a shape's plan is a
+ * pure function of the shape, the workspace and the stream's ticket scratch.
+ * Round 5: which cost model ranks the plans. 4 (default): the
  * round-4 model; 5: chunk-step floor by tile height and up to 256 splits - faster launch by launch, slower where the
  * streams of a loop body overlap. Process-wide; M2D_PLAN_MODEL=4|5 sets the initial value. */
 int m2d_plan_model_set(int model);

@@ -1,5 +1,8 @@
 // Implementation of the separable-gather fp32-MFMA GEMM engine (see gemm_engine.h).
 #include "gemm_engine.h"
+#include <atomic>
+#include <map>
+#include <mutex>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -228,11 +231,7 @@ struct TileMap {
     const int row0 = BR >= 64 ? (__builtin_amdgcn_readfirstlane(tid) & (BR - 1) & ~63) : 0;
     float* dst = img + kb0 * LD + row0;
     if constexpr (UNIFORM) {
-#ifdef M2D_X_NO_WINDOW  // experiment: no window test in uniform chunks
-      const unsigned voff = full;
-#else
       const unsigned voff = ((unsigned)(posr + P) < lim_eff) ? full : M2D_OOB;
-#endif
 #pragma unroll
       for (int i = 0; i < NE; ++i) m2d_bload_lds(rs, dst + (KS * i) * LD, voff, i * ls4);
     } else {
@@ -1192,12 +1191,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 8 : 2) m2d_gemm_dl_kernel(c
       // chunk c + 1 streams into the other stage (every wave left it at the barrier that ended chunk c - 1) while
       // chunk c is multiplied; the chunk after the last one loads zeros or the next split's data, harmlessly
       float* nxt = smem + (cur ^ 1) * STAGE;
-#ifdef M2D_X_UNIFORM_ONLY  // experiment: the loop without its general path (valid for plain GEMMs with K % 16 == 0)
-      {
-        ta.template load_lds<true, BM>(A, ra, cc.hi, cc.lo0, cc.kdiv, nxt, tid);
-        tb.template load_lds<true, BN>(B, rb, cc.hi, cc.lo0, cc.kdiv, nxt + M2D_BK * BM, tid);
-      }
-#else
       if (cc.uniform()) {
         ta.template load_lds<true, BM>(A, ra, cc.hi, cc.lo0, cc.kdiv, nxt, tid);
         tb.template load_lds<true, BN>(B, rb, cc.hi, cc.lo0, cc.kdiv, nxt + M2D_BK * BM, tid);
@@ -1205,13 +1198,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 8 : 2) m2d_gemm_dl_kernel(c
         ta.template load_lds<false, BM>(A, ra, cc.hi, cc.lo0, cc.extent(), nxt, tid);
         tb.template load_lds<false, BN>(B, rb, cc.hi, cc.lo0, cc.extent(), nxt + M2D_BK * BM, tid);
       }
-#endif
       m2d_chunk_mma_dl<BM, BN, NW>(smem + cur * STAGE, wm, wn, l31, lh, acc);
-#ifdef M2D_X_SIMPLE_CURSOR  // experiment: plain GEMM cursor (nhi = 1)
-      cc.lo0 += M2D_BK;
-#else
       cc.next();
-#endif
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
@@ -1774,11 +1762,8 @@ int m2d_rowsums_reduce(const float* part, int P, int M, double* sums, double* sc
 // MFMA chain of one block is then exposed). Split-K costs one slab round trip through HBM plus a
 // second launch. Block counts just above a multiple of 256 leave most CUs idle for the last round,
 // which is why the candidate split factors are the ones that land ON a multiple.
-// With M2D_AUTOTUNE=1 the launcher TIMES the model's few best candidates the first time it meets a
-// shape - on the caller's own operands; every plan writes the same output up to summation order -
-// and keeps the fastest. Measured on the phase-3 step (A/B on one box, 3 runs each): 16.21 vs 16.28 ms,
-// i.e. the model's first choice is already within 0.5 % of the timed best, so timing is OFF by
-// default (plans, and with them summation orders, then do not depend on timing noise).
+// The launchers take the model's first candidate that the workspace and the stream's tickets allow (select_plan):
+// nothing is timed, so plans, and with them summation orders, depend on the shape alone.
 #define M2D_MAX_CAND 6
 
 struct PlanCand {
@@ -1790,7 +1775,6 @@ struct PlanCand {
 // which cost model ranks the plans (m2d_plan_model_set; M2D_PLAN_MODEL overrides the default once at load): 4 = the
 // round-4 model (default: best where a loop body's streams overlap - the two-branch phase-3 critic), 5 = chunk-step floor
 // by tile height + splits up to 256 (best where launches run one after the other: phase 2, the pose-only critic)
-#include <atomic>
 static std::atomic<int> g_plan_model{[] { const char* e = getenv("M2D_PLAN_MODEL"); return (e && e[0] == '5') ? 5 : 4; }()};
 extern "C" int m2d_plan_model_set(int model) {
   if (model != 4 && model != 5) M2D_FAIL(M2D_ERR_ARG, "m2d_plan_model_set: 4 or 5");
@@ -1928,7 +1912,7 @@ extern "C" int m2d_debug_last_plan(int* out) {
 }
 #endif
 
-// The model's first choice; ws_bytes covers every candidate the launcher may time.
+// The model's first choice; ws_bytes covers every candidate the launcher may pick.
 M2dGemmPlan m2d_gemm_plan(int M, int N, int nchunks, int phases, bool allow_split, double small_tile_penalty, int kind) {
   PlanCand c[M2D_MAX_CAND];
   const int n = plan_candidates(M, N, nchunks, phases, allow_split, small_tile_penalty, c, kind);
@@ -2020,8 +2004,6 @@ static int launch_maps(const M2dGemmParams& p, bool akf, bool bkf, dim3 grid, hi
 // The caller registers, once per stream, a zeroed device buffer it keeps alive (m2d_stream_scratch_set); launches on
 // that stream take their tickets from it and leave them zero. Launches of one stream run in order, so one buffer per
 // stream is enough; a stream without one uses the two-launch split-K.
-#include <map>
-#include <mutex>
 static std::mutex g_scratch_mu;
 static std::map<hipStream_t, std::pair<unsigned*, size_t>> g_scratch;
 
@@ -2051,33 +2033,109 @@ extern "C" int m2d_stream_scratch_set(void* stream, void* zeroed, size_t bytes) 
   return M2D_OK;
 }
 
+// ---- plan selection: pure host arithmetic, no HIP call (tests/test_plan_host.py pins it without a GPU) ------------
+// What a launcher asks select_plan: the cost model's inputs, the workspace and the stream's tickets.
+struct PlanQuery {
+  int nchunks, phases;   // K chunks of the longest workgroup; phases of a backward-data launch (1 otherwise)
+  bool allow_split;
+  double small_tile_penalty;
+  int kind;              // M2D_PLAN_*
+  bool k4;               // m2d_conv_k4_launch: tiles of 64 rows at least, (128, 1) where the general launcher fails with
+                         // M2D_ERR_WORKSPACE, and no forced plan in tuning builds
+  void* ws;
+  size_t ws_bytes;
+  unsigned* tickets;     // the stream's zero-kept scratch (m2d_stream_scratch_get), or NULL / 0
+  size_t ticket_bytes;
+  const char* what;
+};
+struct Plan {
+  int bm, splits;
+  unsigned* tickets;     // != NULL: split-K in one launch (m2d_splitk_fixup)
+};
+
 // split-K in one launch when the stream has tickets for every tile, the slab holds whole-tile images and stays under
-// the buffer-addressing limit (M2D_FUSED_SPLITK=0: never)
-static void decide_fused(M2dGemmParams& p, int bm, int splits, const void* ws, size_t ws_bytes, hipStream_t stream) {
+// the buffer-addressing limit (M2D_FUSED_SPLITK=0: never): the tickets, or NULL for the two-launch form
+static unsigned* decide_fused(const M2dGemmParams& p, const PlanQuery& q, int bm, int splits) {
   static const bool on = [] { const char* e = getenv("M2D_FUSED_SPLITK"); return !(e && e[0] == '0'); }();
   static const int max_splits = [] { const char* e = getenv("M2D_FUSE_MAX"); return e ? atoi(e) : M2D_FUSE_MAX_SPLITS; }();  // A/B lever
-  p.tickets = nullptr;
-  if (!on || splits <= 1 || splits > max_splits || p.bwd_data || !ws) return;
+  if (!on || splits <= 1 || splits > max_splits || p.bwd_data || !q.ws) return nullptr;
   const size_t need = m2d_slab_bytes(p.M, p.N, bm, splits);
-  if (need > ws_bytes || need >= 0x7fffffffULL || ((uintptr_t)ws & 15u)) return;
-  size_t sb = 0;
-  unsigned* t = m2d_stream_scratch_get(stream, &sb);
+  if (need > q.ws_bytes || need >= 0x7fffffffULL || ((uintptr_t)q.ws & 15u)) return nullptr;
   const size_t tiles = (size_t)m2d_ceil_div(p.M, bm) * (size_t)m2d_ceil_div(p.N, 128);
-  if (!t || tiles * sizeof(unsigned) > sb) return;
-  p.tickets = t;
+  if (!q.tickets || tiles * sizeof(unsigned) > q.ticket_bytes) return nullptr;
+  return q.tickets;
 }
 
-// would decide_fused take this plan? (Launches with epilogue statistics may split K only in the one-launch form: the
-// workgroup that draws a tile's last ticket holds the whole K and runs the ordinary epilogue, statistics included; the
-// two-launch form's reduction kernel has no statistics pass.)
-static bool fused_possible(const M2dGemmParams& p, int bm, int splits, const void* ws, size_t ws_bytes, hipStream_t stream) {
-  M2dGemmParams q = p;
-  decide_fused(q, bm, splits, ws, ws_bytes, stream);
-  return q.tickets != nullptr;
-}
 static bool stats_split_enabled() {   // A/B lever
   static const bool on = [] { const char* e = getenv("M2D_STATS_SPLIT"); return !(e && e[0] == '0'); }();
   return on;
+}
+
+// The plan of a launch: the model's first candidate whose slabs the workspace holds. Launches with epilogue statistics
+// (p.O.row_part) may split K only in the one-launch form: the workgroup that draws a tile's last ticket holds the whole
+// K and runs the ordinary epilogue, statistics included; the two-launch form's reduction kernel has no statistics pass.
+static int select_plan(const M2dGemmParams& p, const PlanQuery& q, Plan* out) {
+  const bool stats = p.O.row_part != nullptr;
+  const bool allow_split = q.allow_split && !(stats && !stats_split_enabled());
+  const size_t mn4 = (size_t)p.M * (size_t)p.N * sizeof(float);
+  PlanCand cand[M2D_MAX_CAND];
+  int nc = 0;
+  auto first_feasible = [&](bool split) {
+    nc = plan_candidates(p.M, p.N, q.nchunks, q.phases, split, q.small_tile_penalty, cand, q.kind);
+    for (int i = 0; i < nc; ++i) {
+      const int bm = q.k4 && cand[i].bm < 64 ? 64 : cand[i].bm, splits = cand[i].splits;
+      unsigned* const t = decide_fused(p, q, bm, splits);
+      if (splits > 1 && ((stats && !t) || !q.ws || q.ws_bytes < splits * mn4)) continue;
+      *out = {bm, splits, t};
+      return true;
+    }
+    return false;
+  };
+  bool found = first_feasible(allow_split);
+  if (!found && q.k4) {
+    *out = {128, 1, nullptr};
+    return M2D_OK;
+  }
+  // statistics, and every plan of the model splits K beyond the one-launch form: plan without
+  if (!found && stats && allow_split) found = first_feasible(false);
+  if (!found) {
+    if (nc > 0)
+      M2D_FAIL(M2D_ERR_WORKSPACE, "%s: split-K needs %zu workspace bytes, got %zu", q.what, cand[0].splits * mn4, q.ws_bytes);
+    M2D_FAIL(M2D_ERR_ARG, "%s: no launch plan", q.what);
+  }
+#ifdef M2D_TUNING
+  if (!q.k4 && getenv("M2D_PLAN")) {
+    const M2dGemmPlan fp = m2d_gemm_plan(p.M, p.N, q.nchunks, q.phases, allow_split, q.small_tile_penalty, q.kind);
+    if (fp.splits > 1 && (!q.ws || q.ws_bytes < fp.splits * mn4))
+      M2D_FAIL(M2D_ERR_WORKSPACE, "%s: forced plan needs more workspace", q.what);
+    *out = {fp.bm, fp.splits, decide_fused(p, q, fp.bm, fp.splits)};
+  }
+#endif
+  if (p.tall_last_rb) *out = {128, 1, nullptr};  // the phase-major sub-pixel launch: whole 128-row tiles, whole K
+  return M2D_OK;
+}
+
+// test-only (tests/test_plan_host.py binds it with ctypes; not part of include/m2d.h): the plan `launcher` (0
+// m2d_gemm_launch, 1 m2d_conv_k4_launch) would take, from plain numbers; out = {rc, bm, splits, fused}. Touches no
+// stream and no device: the pointers it makes up are only tested for NULL and alignment.
+extern "C" void m2d_debug_select_plan(int launcher, int M, int N, int nchunks, int phases, int allow_split, double penalty,
+                                      int kind, int bwd_data, int has_stats, size_t ws_bytes, int ws_aligned,
+                                      size_t ticket_bytes, int tall_last_rb, int* out) {
+  M2dGemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.M = M;
+  p.N = N;
+  p.bwd_data = bwd_data;
+  p.tall_last_rb = tall_last_rb;
+  p.O.row_part = has_stats ? (float*)(uintptr_t)256 : nullptr;
+  const PlanQuery q = {nchunks, phases, allow_split != 0, penalty, kind, launcher == 1,
+                       ws_bytes ? (void*)(uintptr_t)(ws_aligned ? 256 : 260) : nullptr, ws_bytes,
+                       ticket_bytes ? (unsigned*)(uintptr_t)256 : nullptr, ticket_bytes, "m2d_debug_select_plan"};
+  Plan pl = {0, 0, nullptr};
+  out[0] = select_plan(p, q, &pl);
+  out[1] = pl.bm;
+  out[2] = pl.splits;
+  out[3] = pl.tickets != nullptr;
 }
 
 static int stats_narrow_fast_default() {   // A/B lever
@@ -2088,45 +2146,6 @@ static int stats_narrow_fast_default() {   // A/B lever
 static int tile_map_default() {
   static const int v = [] { const char* e = getenv("M2D_TILE_MAP"); return e ? atoi(e) : 1; }();
   return v;
-}
-
-// one launch of the GEMM (+ the slab reduction) under plan (bm, splits)
-static int plan_run(M2dGemmParams& p, int bm, int splits, bool a_kfast, bool b_kfast, void* ws, hipStream_t stream) {
-  p.splits = splits;
-  p.tile_map = tile_map_default();
-  p.stats_narrow_fast = stats_narrow_fast_default();
-  p.slab = splits > 1 ? (float*)ws : nullptr;
-  const int mt = m2d_ceil_div(p.M, bm);
-  const long long nt = m2d_ceil_div(p.N, 128);
-  const dim3 grid((unsigned)nt, (unsigned)mt, (unsigned)(p.bwd_data ? p.phases : splits));
-  int lrc;
-  if (bm == 32) lrc = launch_maps<32>(p, a_kfast, b_kfast, grid, stream);
-  else if (bm == 64) lrc = launch_maps<64>(p, a_kfast, b_kfast, grid, stream);
-  else lrc = launch_maps<128>(p, a_kfast, b_kfast, grid, stream);
-  if (lrc) return lrc;
-  if (splits > 1 && !p.tickets) {
-    const size_t total = (size_t)p.M * p.N;
-    unsigned blocks = (unsigned)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(m2d_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
-  }
-  return 0;
-}
-
-// ---- plan cache: shape -> fastest timed plan --------------------------------------------------
-#include <map>
-#include <mutex>
-#include <vector>
-static std::mutex g_plan_mu;
-static std::map<std::vector<int>, std::pair<int, int>> g_plan_cache;
-
-static bool autotune_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("M2D_AUTOTUNE");
-    on = (e && e[0] == '1') ? 1 : 0;
-  }
-  return on == 1;
 }
 
 // 16-byte epilogue rows (m2d_tile_epilogue, WIDE) when the output map allows it (M2D_WIDE_EPILOGUE=0: never)
@@ -2145,6 +2164,50 @@ static void decide_wide(M2dGemmParams& p, int splits, const void* ws) {
   p.O.wide = w ? 1 : 0;
 }
 
+// Plan and run one launch: the launcher-owned fields of `p`, the grid through `launch_grid(bm, grid)` (non-zero: no kernel
+// for these operand maps), the slab reduction of a two-launch split-K, the row-sums reduction of the epilogue statistics.
+template <class LaunchGrid>
+static int plan_and_launch(M2dGemmParams& p, PlanQuery& q, hipStream_t stream, double flops, LaunchGrid launch_grid) {
+  const char* what = q.what;
+  void* const ws = q.ws;
+  q.tickets = q.allow_split ? m2d_stream_scratch_get(stream, &q.ticket_bytes) : nullptr;
+  Plan pl;
+  if (const int rc = select_plan(p, q, &pl)) return rc;
+  const int bm = pl.bm, splits = pl.splits;
+  // (the model cannot get here; a forced plan of a tuning build can)
+  if (p.O.row_part && splits > 1 && !pl.tickets)
+    M2D_FAIL(M2D_ERR_ARG, "%s: epilogue statistics need split-K in one launch (plan %d x %d has no tickets)", what, bm, splits);
+#ifdef M2D_TUNING
+  {
+    const int lp[9] = {p.M, p.N, q.nchunks, q.phases, (int)q.allow_split, (int)((float)q.small_tile_penalty * 100.f), bm, splits, q.kind};
+    memcpy(g_last_plan, lp, sizeof(lp));
+  }
+#endif
+  p.splits = splits;
+  p.tile_map = tile_map_default();
+  p.stats_narrow_fast = stats_narrow_fast_default();
+  p.slab = splits > 1 ? (float*)ws : nullptr;
+  p.tickets = pl.tickets;
+  decide_wide(p, splits, ws);
+  const dim3 grid((unsigned)m2d_ceil_div(p.N, 128), (unsigned)m2d_ceil_div(p.M, bm), (unsigned)(p.bwd_data ? p.phases : splits));
+  M2dProfScope prof(M2D_FAM_GEMM, stream, flops, 0.0, what, p.M, p.N, p.K);
+  if (launch_grid(bm, grid)) M2D_FAIL(M2D_ERR_ARG, "%s: unsupported operand map combination", what);
+  if (splits > 1 && !p.tickets) {
+    const size_t total = (size_t)p.M * p.N;
+    unsigned blocks = (unsigned)((total + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(m2d_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
+  }
+  M2D_CHECK_LAUNCH(what);
+  if (p.O.row_part) {
+    if (!p.O.row_sums) M2D_FAIL(M2D_ERR_ARG, "%s: row statistics without a destination", what);
+    // partials per row: one per 32-column tile of every N tile
+    return m2d_rowsums_reduce(p.O.row_part, m2d_ceil_div(p.N, 128) * 4, p.M, p.O.row_sums,
+                              m2d_rowstats_scratch(p.O.row_part, p.M, p.N), stream);
+  }
+  return M2D_OK;
+}
+
 int m2d_gemm_launch(M2dGemmParams& p, bool a_kfast, bool b_kfast, bool allow_split, void* ws,
                     size_t ws_bytes, hipStream_t stream, const char* what) {
   if (p.M <= 0 || p.N <= 0) return M2D_OK;
@@ -2152,12 +2215,16 @@ int m2d_gemm_launch(M2dGemmParams& p, bool a_kfast, bool b_kfast, bool allow_spl
     M2D_FAIL(M2D_ERR_RANGE, "%s: operand larger than 2 GiB (buffer addressing) or empty", what);
   if (p.M >= (1 << 24) || p.N >= (1 << 24))
     M2D_FAIL(M2D_ERR_RANGE, "%s: extent >= 2^24 (row decomposition is exact below that)", what);
+  if (m2d_ceil_div(p.M, 32) > 65535) M2D_FAIL(M2D_ERR_RANGE, "%s: M too large (%d)", what, p.M);
   if (p.kdiv <= 0 || p.nhi < 0 || p.A.k_lo_stride < 0 || p.B.k_lo_stride < 0)
     M2D_FAIL(M2D_ERR_ARG, "%s: bad contraction map (kdiv=%d nhi=%d)", what, p.kdiv, p.nhi);
   if ((a_kfast && p.A.lim > 0) || (b_kfast && p.B.lim > 0))
     M2D_FAIL(M2D_ERR_ARG, "%s: k-fast operands carry no window", what);
   if (!((a_kfast && !b_kfast) || (!a_kfast && !b_kfast) || (a_kfast && b_kfast)))
     M2D_FAIL(M2D_ERR_ARG, "%s: unsupported operand map combination", what);
+  if (p.tall_last_rb && (p.tall_last_rb != 1 || p.M % 128 != 0 || !p.lo_outer || p.O.bias_mode || p.O.act || !p.O.mask_last ||
+                         !dl_enabled() || !dl_eligible(p, a_kfast, b_kfast)))
+    M2D_FAIL(M2D_ERR_ARG, "%s: bad phase-major sub-pixel launch", what);
   if (p.phases < 1) p.phases = 1;
   {
     // the epilogue addresses out / mask / residual / sum_out with 32-bit byte offsets: the map must stay below 2 GiB
@@ -2171,105 +2238,8 @@ int m2d_gemm_launch(M2dGemmParams& p, bool a_kfast, bool b_kfast, bool allow_spl
   }
   // bwd_data: the widest phase has ceil(ks / phases) taps
   const int nhi_max = p.bwd_data ? (p.ph_ks + p.phases - 1) / p.phases : p.nhi;
-  const int nchunks = m2d_chunks(nhi_max, p.kdiv);
-  // the statistics come out of the tile epilogue: split K only where the last arriver of a tile runs it (fused_possible)
-  if (p.O.row_part && !stats_split_enabled()) allow_split = false;
-  PlanCand cand[M2D_MAX_CAND];
-  int nc = plan_candidates(p.M, p.N, nchunks, p.bwd_data ? p.phases : 1, allow_split, p.small_tile_penalty, cand, p.plan_kind);
-  {
-    // a split plan needs its slabs: drop the ones the workspace cannot hold
-    int k = 0;
-    for (int i = 0; i < nc; ++i) {
-      const size_t need = cand[i].splits > 1 ? (size_t)cand[i].splits * (size_t)p.M * (size_t)p.N * sizeof(float) : 0;
-      if (p.O.row_part && cand[i].splits > 1 && !fused_possible(p, cand[i].bm, cand[i].splits, ws, ws_bytes, stream)) continue;
-      if (need == 0 || (ws != nullptr && ws_bytes >= need)) cand[k++] = cand[i];
-    }
-    if (k == 0 && p.O.row_part && allow_split) {   // every plan of the model splits K beyond the one-launch form: plan without
-      nc = plan_candidates(p.M, p.N, nchunks, p.bwd_data ? p.phases : 1, false, p.small_tile_penalty, cand, p.plan_kind);
-      k = nc;
-    }
-    if (k == 0) {
-      if (nc > 0)
-        M2D_FAIL(M2D_ERR_WORKSPACE, "%s: split-K needs %zu workspace bytes, got %zu", what,
-                 (size_t)cand[0].splits * (size_t)p.M * (size_t)p.N * sizeof(float), ws_bytes);
-      M2D_FAIL(M2D_ERR_ARG, "%s: no launch plan", what);
-    }
-    nc = k;
-  }
-  if (m2d_ceil_div(p.M, 32) > 65535) M2D_FAIL(M2D_ERR_RANGE, "%s: M too large (%d)", what, p.M);
-  int bm = cand[0].bm, splits = cand[0].splits;
-#ifdef M2D_TUNING
-  const char* forced = getenv("M2D_PLAN");
-  if (forced) {
-    const M2dGemmPlan fp = m2d_gemm_plan(p.M, p.N, nchunks, p.bwd_data ? p.phases : 1, allow_split, p.small_tile_penalty, p.plan_kind);
-    bm = fp.bm;
-    splits = fp.splits;
-    if (splits > 1 && (!ws || ws_bytes < (size_t)splits * p.M * p.N * sizeof(float)))
-      M2D_FAIL(M2D_ERR_WORKSPACE, "%s: forced plan needs more workspace", what);
-  } else
-#endif
-  if (autotune_enabled() && nc > 1 && !p.tall_last_rb) {   // (the phase-major launch has ONE plan: nothing to time)
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone;
-    std::vector<int> key;
-    key.reserve(40);
-    for (const char* c = what; *c; ++c) key.push_back((int)*c);
-    const int kf[] = {p.M, p.N, nchunks, p.bwd_data ? p.phases : 1, (int)a_kfast, (int)b_kfast,
-                      (int)(p.A.mask || p.B.mask), (int)allow_split, p.lo_outer, p.kdiv, p.A.k_lo_stride,
-                      p.B.k_lo_stride, p.B.r_lo_stride, (int)(p.small_tile_penalty * 100.f), nc,
-                      cand[nc - 1].bm, cand[nc - 1].splits};
-    key.insert(key.end(), kf, kf + sizeof(kf) / sizeof(int));
-    std::unique_lock<std::mutex> lk(g_plan_mu);
-    auto it = g_plan_cache.find(key);
-    if (it != g_plan_cache.end()) {
-      bm = it->second.first;
-      splits = it->second.second;
-    } else if (!capturing) {
-      lk.unlock();
-      // time every candidate on the real operands; two runs each, the faster one counts
-      hipEvent_t e0, e1;
-      if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-        float best_ms = 1e30f;
-        for (int i = 0; i < nc; ++i) {
-          float ms = 1e30f;
-          for (int rep = 0; rep < 2; ++rep) {
-            (void)hipEventRecord(e0, stream);
-            if (plan_run(p, cand[i].bm, cand[i].splits, a_kfast, b_kfast, ws, stream)) break;
-            (void)hipEventRecord(e1, stream);
-            if (hipEventSynchronize(e1) != hipSuccess) break;
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, e0, e1) == hipSuccess && t < ms) ms = t;
-          }
-          if (ms < best_ms) {
-            best_ms = ms;
-            bm = cand[i].bm;
-            splits = cand[i].splits;
-          }
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        M2D_CHECK_LAUNCH(what);
-      }
-      lk.lock();
-      g_plan_cache[key] = std::make_pair(bm, splits);
-    }
-  }
-  if (p.tall_last_rb) {  // the phase-major sub-pixel launch: whole 128-row tiles, whole K
-    if (p.tall_last_rb != 1 || p.M % 128 != 0 || !p.lo_outer || p.O.bias_mode || p.O.act || !p.O.mask_last || !dl_enabled() ||
-        !dl_eligible(p, a_kfast, b_kfast))
-      M2D_FAIL(M2D_ERR_ARG, "%s: bad phase-major sub-pixel launch", what);
-    bm = 128;
-    splits = 1;
-  }
-#ifdef M2D_TUNING
-  {
-    const int lp[9] = {p.M, p.N, nchunks, p.bwd_data ? p.phases : 1, (int)allow_split, (int)(p.small_tile_penalty * 100.f), bm, splits,
-                       p.plan_kind};
-    memcpy(g_last_plan, lp, sizeof(lp));
-  }
-#endif
-  decide_fused(p, bm, splits, ws, ws_bytes, stream);
-  decide_wide(p, splits, ws);
+  PlanQuery q = {m2d_chunks(nhi_max, p.kdiv), p.bwd_data ? p.phases : 1, allow_split, p.small_tile_penalty, p.plan_kind,
+                 false, ws, ws_bytes, nullptr, 0, what};
   double flops = p.work_flops > 0.0 ? p.work_flops : 2.0 * p.M * (double)p.N * p.K;
   if (p.bwd_data) {
     flops = 0.0;
@@ -2281,21 +2251,11 @@ int m2d_gemm_launch(M2dGemmParams& p, bool a_kfast, bool b_kfast, bool allow_spl
       if (nq > 0) flops += 2.0 * p.M * (double)p.ph_batch * nq * p.ph_cout * taps;
     }
   }
-  {
-    M2dProfScope prof(M2D_FAM_GEMM, stream, flops, 0.0, what, p.M, p.N, p.K);
-    if (plan_run(p, bm, splits, a_kfast, b_kfast, ws, stream))
-      M2D_FAIL(M2D_ERR_ARG, "%s: unsupported operand map combination", what);
-    M2D_CHECK_LAUNCH(what);
-    if (p.O.row_part) {
-      if (!p.O.row_sums) M2D_FAIL(M2D_ERR_ARG, "%s: row statistics without a destination", what);
-      // partials per row: one per wave column of every N tile; the 16-byte epilogue writes one per 32-column tile
-      const int wn = 4;  // one per 32-column tile
-      const int rc = m2d_rowsums_reduce(p.O.row_part, m2d_ceil_div(p.N, 128) * wn, p.M, p.O.row_sums,
-                                        m2d_rowstats_scratch(p.O.row_part, p.M, p.N), stream);
-      if (rc) return rc;
-    }
-  }
-  return M2D_OK;
+  return plan_and_launch(p, q, stream, flops, [&](int bm, dim3 grid) {
+    return bm == 32 ? launch_maps<32>(p, a_kfast, b_kfast, grid, stream)
+         : bm == 64 ? launch_maps<64>(p, a_kfast, b_kfast, grid, stream)
+                    : launch_maps<128>(p, a_kfast, b_kfast, grid, stream);
+  });
 }
 
 template <int BM>
@@ -2310,53 +2270,10 @@ int m2d_conv_k4_launch(M2dGemmParams& p, bool allow_split, void* ws, size_t ws_b
   if (p.A.nbytes == 0 || p.B.nbytes == 0 || p.k4_ng <= 0)
     M2D_FAIL(M2D_ERR_RANGE, "%s: operand larger than 2 GiB (buffer addressing), empty, or no tap groups", what);
   if (p.M >= (1 << 24) || p.N >= (1 << 24)) M2D_FAIL(M2D_ERR_RANGE, "%s: extent >= 2^24", what);
-  const int nchunks = (p.nhi * p.k4_ng + 3) / 4;
-  if (p.O.row_part && !stats_split_enabled()) allow_split = false;
-  PlanCand cand[M2D_MAX_CAND];
-  const int nc = plan_candidates(p.M, p.N, nchunks, 1, allow_split, 1.0, cand);
-  int bm = 128, splits = 1;
-  for (int i = 0; i < nc; ++i) {
-    const size_t need = cand[i].splits > 1 ? (size_t)cand[i].splits * (size_t)p.M * (size_t)p.N * sizeof(float) : 0;
-    // (statistics: one-launch split-K only, see m2d_gemm_launch)
-    if (p.O.row_part && cand[i].splits > 1 &&
-        !fused_possible(p, cand[i].bm < 64 ? 64 : cand[i].bm, cand[i].splits, ws, ws_bytes, stream)) continue;
-    if (need == 0 || (ws != nullptr && ws_bytes >= need)) {
-      bm = cand[i].bm < 64 ? 64 : cand[i].bm;
-      splits = cand[i].splits;
-      break;
-    }
-  }
-  p.splits = splits;
-  p.tile_map = tile_map_default();
-  p.stats_narrow_fast = stats_narrow_fast_default();
-  p.slab = splits > 1 ? (float*)ws : nullptr;
-  decide_fused(p, bm, splits, ws, ws_bytes, stream);
-  decide_wide(p, splits, ws);
-  const dim3 grid((unsigned)m2d_ceil_div(p.N, 128), (unsigned)m2d_ceil_div(p.M, bm), (unsigned)splits);
-  {
-    M2dProfScope prof(M2D_FAM_GEMM, stream, 2.0 * p.M * (double)p.N * p.K, 0.0, what, p.M, p.N, p.K);
+  PlanQuery q = {(p.nhi * p.k4_ng + 3) / 4, 1, allow_split, 1.0, M2D_PLAN_GENERAL, true, ws, ws_bytes, nullptr, 0, what};
+  return plan_and_launch(p, q, stream, 2.0 * p.M * (double)p.N * p.K, [&](int bm, dim3 grid) {
     if (bm == 64) k4_launch_tile<64>(p, grid, stream);
     else k4_launch_tile<128>(p, grid, stream);
-    if (splits > 1 && !p.tickets) {
-      const size_t total = (size_t)p.M * p.N;
-      unsigned blocks = (unsigned)((total + 255) / 256);
-      if (blocks > 2048) blocks = 2048;
-      hipLaunchKernelGGL(m2d_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
-    }
-    M2D_CHECK_LAUNCH(what);
-    if (p.O.row_part) {
-      if (!p.O.row_sums) M2D_FAIL(M2D_ERR_ARG, "%s: row statistics without a destination", what);
-      const int wn = 4;  // one per 32-column tile
-      const int rc = m2d_rowsums_reduce(p.O.row_part, m2d_ceil_div(p.N, 128) * wn, p.M, p.O.row_sums,
-                                        m2d_rowstats_scratch(p.O.row_part, p.M, p.N), stream);
-      if (rc) return rc;
-    }
-  }
-  return M2D_OK;
-}
-
-// number of operand shapes with a timed launch plan (diagnostics)
-extern "C" int m2d_plan_cache_size(void) {
-  std::lock_guard<std::mutex> lk(g_plan_mu);
-  return (int)g_plan_cache.size();
+    return 0;
+  });
 }

@@ -639,7 +639,7 @@ def test_conv1d_over_track_windows_equals_conv_on_materialised_slices(case):
                                   ("wavegan.l1-thin", 12, 1, 3200, 32, 25, 4, 0), ("wavegan.l2", 6, 32, 794, 64, 25, 4, 0),
                                   ("unet.cb", 5, 128, 200, 128, 3, 1, 1), ("odd", 7, 19, 37, 21, 5, 2, 2),
                                   # few tiles, long K: the planner splits K; the statistics then come from the tile's last
-                                  # arriver (one-launch split-K, csrc/gemm_engine.hip: fused_possible) - WaveGAN l4 at B = 32
+                                  # arriver (one-launch split-K, csrc/gemm_engine.hip: select_plan) - WaveGAN l4 at B = 32
                                   ("unet.c0-k160", 10, 1, 3200, 32, 160, 4, 79),
                                   ("wavegan.l4-splitK", 30, 128, 2560, 256, 25, 4, 11), ("splitK-8-tiles", 4, 256, 512, 256, 25, 4, 11)],
                          ids=lambda c: c[0])
@@ -848,6 +848,42 @@ def test_split_k_in_one_launch_equals_the_two_launch_form():
     # and again on the registered stream: the tickets a launch left behind serve the next one
     gw_again = k.conv1d_bwd_weight(x, dy, ks, s, p)
     assert torch.equal(gw_again, gw_fused)
+
+
+def test_epilogue_statistics_with_and_without_the_streams_tickets():
+    """A forward conv with epilogue statistics whose plan splits K (one output tile, 56 K chunks): with the stream's
+    tickets the split finishes in one launch and the tile's last arriver takes the statistics; without them the launch
+    must run unsplit - the two-launch form's reduction has no statistics pass. Both give y and the sums."""
+    from music2dance_amd import _lib, kernels
+    from tests import plan_cases as C
+    k = K()
+    conv = B, Cin, L, Cout, ks, s, p = 2, 128, 16, 64, 7, 1, 3
+    M, N, nchunks = Cout, B * L, ks * (Cin // 16)
+    ws = C.launcher_ws_bytes("fwd_stats", conv, M, N)
+    rc, _, splits, fused = C.select_plan(C.GENERAL, M, N, nchunks, 1, 1, 1.0, 0, 0, 1, ws, True, C.TICKET_BYTES)
+    assert rc == 0 and splits > 1 and fused == 1    # the shape does split when there are tickets ...
+    assert C.select_plan(C.GENERAL, M, N, nchunks, 1, 1, 1.0, 0, 0, 1, ws, True, 0)[:3:2] == (0, 1)   # ... and not without
+    x = gen(B, Cin, L, seed=1).to(DEV)
+    w = (gen(Cout, Cin, ks, seed=2) / math.sqrt(Cin * ks)).to(DEV)
+    bias = gen(Cout, seed=3, scale=0.1).to(DEV)
+    ref = F.conv1d(x.double().cpu(), w.double().cpu(), bias.double().cpu(), stride=s, padding=p)
+    stream = kernels._stream(torch.device(DEV))  # registers the scratch
+    key = (torch.device(DEV).index, stream)
+    t = kernels._STREAM_SCRATCH[key]
+    y_one, sums_one = k.conv1d_fwd(x, w, bias, s, p, with_stats=True)
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().m2d_stream_scratch_set(stream, 0, 0), "m2d_stream_scratch_set")
+    try:
+        y_un, sums_un = k.conv1d_fwd(x, w, bias, s, p, with_stats=True)
+        torch.cuda.synchronize()
+    finally:
+        _lib.check(_lib.lib().m2d_stream_scratch_set(stream, t.data_ptr(), t.numel() * 4), "m2d_stream_scratch_set")
+    assert int(t.abs().sum().item()) == 0  # the tickets are left zero
+    for y, sums in ((y_one, sums_one), (y_un, sums_un)):
+        y64 = y.double()
+        assert rel_err(y, ref) <= 2e-5
+        assert rel_err(sums[0::2], y64.sum((0, 2))) < 1e-6 and rel_err(sums[1::2], (y64 * y64).sum((0, 2))) < 1e-6
+    assert rel_err(y_one, y_un.double()) <= 2e-6
 
 
 def test_a_timed_out_recurrence_voids_the_queued_optimizer_steps_and_the_run_goes_on():
