@@ -140,6 +140,19 @@ class WganGpEngine:
         self._graphs = {}
         self._graphs_gen = int(getattr(k, "async_faults", 0))
 
+    def _manual_critic(self, step_cls, *args, **kw):
+        """-> step_cls(critic, ...) (critic_step.py) if the critic qualifies and M2D_MANUAL_CRITIC is not 0, else None"""
+        if os.environ.get("M2D_MANUAL_CRITIC", "1") == "0" or not step_cls.supports(self.critic):
+            return None
+        step = step_cls(self.critic, *args, **kw)
+        if hasattr(step, "join_pairs"):
+            step.join_pairs = self._join_pairs
+        return step
+
+    def _channels_first(self, x, B, T):
+        """(B, T, C) poses or (B*T, C) rows -> a contiguous (B, C, T) copy"""
+        return x.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+
     # -- critic optimiser step, possibly deferred so its all-reduce overlaps the next G forward
     def _finish_critic_step(self):
         if self._critic_step_pending:
@@ -447,9 +460,7 @@ class Phase3Engine(WganGpEngine):
         # M2D_REUSE_AUDIO_PATH=0: both passes in full, as the reference executes them.
         self.reuse_audio_path = (os.environ.get("M2D_REUSE_AUDIO_PATH", "1") != "0"
                                  and hasattr(gen, "forward_keeping_audio_path"))
-        if os.environ.get("M2D_MANUAL_CRITIC", "1") != "0" and CriticStep.supports(critic):
-            self.manual_critic = CriticStep(critic, self.gamma, lp=False)
-            self.manual_critic.join_pairs = self._join_pairs
+        self.manual_critic = self._manual_critic(CriticStep, self.gamma, lp=False)
 
     def _shapes(self, real):
         B = real.size(0)
@@ -503,13 +514,13 @@ class Phase3Engine(WganGpEngine):
                 alpha = to_device_async(torch.rand(B, 1), real.device)
             return self.manual_critic.run(real, fake_rows, None if self.ablated else audio_c, alpha,
                                           on_grads=self._poll_exchange(), fake_ready=fake_ready)
-        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        real_c = self._channels_first(real, B, T)
         with self.critic.shared_audio() if not self.ablated else contextlib.nullcontext():
             self._join_generator_forward(fake_rows)
             return self._critic_passes(B, T, real, real_c, fake_rows, audio_c, alpha)
 
     def _critic_passes(self, B, T, real, real_c, fake_rows, audio_c, alpha):
-        fake = fake_rows.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        fake = self._channels_first(fake_rows, B, T)
         if self.ablated:
             gp = gradient_penalty(self.critic, B, real_c, fake, is_seq=True, lp=False, device=real.device, alpha=alpha)
             s_real, s_fake = self.critic.score_pair(real_c, fake)
@@ -559,7 +570,7 @@ class Phase3Engine(WganGpEngine):
         real_rows = real.reshape(B * T, self.output_size)
         err_l1 = ops.l1_mean(real_rows, fake_rows)
         fake = fake_rows.view(B, T, self.output_size).permute(0, 2, 1)
-        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        real_c = self._channels_first(real, B, T)
         audio_c = audio.unsqueeze(1)
         with _Freeze(self.critic):
             if self.ablated:
@@ -651,9 +662,7 @@ class Phase2Engine(WganGpEngine):
         self.scheduler_gen = optim.lr_scheduler.MultiStepLR(self.optim_gen, milestones=ms, gamma=0.8)
         self.host_noise = True  # draw noise on the host generator (matches the CPU reference)
         self._ready0 = None     # _always_ready
-        if os.environ.get("M2D_MANUAL_CRITIC", "1") != "0" and CriticStep.supports(critic):
-            self.manual_critic = CriticStep(critic, self.gamma, lp=True)
-            self.manual_critic.join_pairs = self._join_pairs
+        self.manual_critic = self._manual_critic(CriticStep, self.gamma, lp=True)
 
     def _shapes(self, real):
         B = real.size(0)
@@ -696,8 +705,8 @@ class Phase2Engine(WganGpEngine):
             if alpha is None:
                 alpha = to_device_async(torch.rand(B, 1), real.device)  # host draw, as losses.py:15
             return self.manual_critic.run(real, fake_rows, None, alpha, on_grads=self._poll_exchange())
-        fake = fake_rows.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
-        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        fake = self._channels_first(fake_rows, B, T)
+        real_c = self._channels_first(real, B, T)
         gp = gradient_penalty(self.critic, B, real_c, fake, is_seq=True, lp=True, device=real.device, alpha=alpha)
         s_real, s_fake = self.critic.score_pair(real_c, fake)
         err_real, err_fake = s_real.mean(), s_fake.mean()
@@ -723,7 +732,7 @@ class Phase2Engine(WganGpEngine):
         if noise is None:
             noise = self._noise(B, T, real.device)
         fake = self.gen(noise, [T] * B).view(B, T, self.output_size).permute(0, 2, 1)
-        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        real_c = self._channels_first(real, B, T)
         with _Freeze(self.critic):
             with torch.no_grad():
                 err_real = self.critic(real_c).mean()
@@ -812,17 +821,15 @@ class Phase2GanEngine(Phase2Engine):
         cfg = dict(cfg, n_critic_steps=1)   # (whatever the YAML says)
         cfg.setdefault("gamma", 0.0)          # (no penalty)
         super().__init__(gen, critic, cfg, **kw)
-        self.manual_critic = None
-        if os.environ.get("M2D_MANUAL_CRITIC", "1") != "0" and GanCriticStep.supports(critic):
-            self.manual_critic = GanCriticStep(critic)
+        self.manual_critic = self._manual_critic(GanCriticStep)
 
     def _critic_from_fake(self, real, fake_rows, alpha=None):
         """err_critic = BCE(critic(real), 1) + BCE(critic(fake), 0) (phase2/train.py:217-219); `alpha` is not used."""
         B, T = self._shapes(real)
         if self.manual_critic is not None:
             return self.manual_critic.run(real, fake_rows, on_grads=self._poll_exchange())
-        fake = fake_rows.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
-        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        fake = self._channels_first(fake_rows, B, T)
+        real_c = self._channels_first(real, B, T)
         s_real, s_fake = self.critic.score_pair(real_c, fake)
         err_real, err_fake = bce_with_logits(s_real, 1.0), bce_with_logits(s_fake, 0.0)
         err_critic = err_real + err_fake
@@ -864,9 +871,7 @@ class Phase2CondEngine(Phase2Engine):
 
     def __init__(self, gen, critic, cfg, **kw):
         super().__init__(gen, critic, cfg, **kw)
-        self.manual_critic = None
-        if os.environ.get("M2D_MANUAL_CRITIC", "1") != "0" and CondCriticStep.supports(critic):
-            self.manual_critic = CondCriticStep(critic, self.gamma, lp=True)
+        self.manual_critic = self._manual_critic(CondCriticStep, self.gamma, lp=True)
 
     @property
     def host_noise(self):
@@ -943,8 +948,8 @@ class Phase2CondEngine(Phase2Engine):
         if self.manual_critic is not None:
             return self.manual_critic.run(real, fake_rows, real_labels, fake_lbl, alpha,
                                           keep=self._critic_keep(B, T, real.device), on_grads=self._poll_exchange())
-        fake = fake_rows.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
-        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        fake = self._channels_first(fake_rows, B, T)
+        real_c = self._channels_first(real, B, T)
         gp = gradient_penalty(self.critic, B, real_c, fake, is_seq=True, lp=True, device=real.device, alpha=alpha,
                               labels=real_labels)
         err_real = self.critic(real_c, real_labels).mean()
@@ -967,7 +972,7 @@ class Phase2CondEngine(Phase2Engine):
         if noise is None:
             noise = self._noise(B, T, dev)
         fake = self.gen(noise, lbl).view(B, T, self.output_size).permute(0, 2, 1)
-        real_c = real.view(B, T, self.output_size).permute(0, 2, 1).contiguous()
+        real_c = self._channels_first(real, B, T)
         with _Freeze(self.critic):
             with torch.no_grad():
                 err_real = self.critic(real_c, real_labels).mean()
