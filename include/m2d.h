@@ -493,6 +493,54 @@ int m2d_beat_align(const float* onset, const float* speed, int B, int T, double 
                    double sigma_align, float* scores, unsigned char* motion_events, unsigned char* music_events,
                    float* onset_smooth, float* speed_smooth, void* stream);
 
+/* ---- distribution scores of a set of dances (metrics.py; no counterpart in the reference) ------
+ * Here `mean`, `cov`, the matrices, eigenvalues and scores are DOUBLE; every sum has a fixed order (no atomics): results
+ * are bit-identical from run to run. A null or a host pointer is refused (M2D_ERR_ARG, nothing launched).
+ *
+ * Kinetic features of poses (B, T, J, 3), contiguous, T >= 3, fps > 0, up_axis in 0..2. With d[t] = p[t] - p[t - 1]
+ * (taken in fp32), v[t] = d[t] fps and a[t] = (d[t + 1] - d[t]) fps^2 (the second difference, also fp32), joint j gives
+ *   F[b][j]         = mean over t = 1 .. T - 1 of v[t][o1]^2 + v[t][o2]^2  (o1 < o2 the axes other than up_axis),
+ *   F[b][J + j]     = mean over t = 1 .. T - 1 of v[t][up_axis]^2,
+ *   F[b][2 J + j]   = mean over t = 1 .. T - 2 of sqrt((a[t][o1]^2 + a[t][o2]^2) + a[t][up_axis]^2),
+ * products and sums in fp64 (256 interleaved partial sums, then a tree), rounded to fp32 once. One workgroup per (b, j):
+ * row b does not depend on B. M2D_ERR_ARG: B or J <= 0, T < 3, fps <= 0, up_axis outside 0..2. */
+int m2d_kinetic_features(const float* poses, int B, int T, int J, double fps, int up_axis, float* F, void* stream);
+/* the largest order m2d_sym_eig, m2d_feature_moments and m2d_frechet take (128), and the sweep cap of the solver (30) */
+int m2d_sym_eig_max_dim(void);
+int m2d_sym_eig_max_sweeps(void);
+/* mean (D) and unbiased covariance (D, D) of the rows of X (N, D) fp32, rows ldx floats apart: two passes,
+ *   mean[d] = (1 / N) sum_n x[n][d],  cov[i][j] = (1 / (N - 1)) sum_n (x[n][i] - mean[i]) (x[n][j] - mean[j]),
+ * every operation fp64 (the second sum in ascending n with fma): cov is exactly symmetric.
+ * M2D_ERR_ARG: N < 2, D outside [1, max_dim], ldx < D. */
+int m2d_feature_moments(const float* X, long long ldx, int N, int D, double* mean, double* cov, void* stream);
+/* Eigenvalues w (P, D), ascending, of P symmetric matrices A (P, D, D) (the whole matrix is read), and with vecs != NULL
+ * the eigenvectors as the COLUMNS of vecs (P, D, D): A vecs[:, i] = w[i] vecs[:, i]. Two-sided cyclic Jacobi in a
+ * round-robin ordering, one workgroup per matrix, the matrix in LDS. info (P, 2): [sweeps used, converged (1 / 0)].
+ * Converged: the squared off-diagonal norm a sweep met is at most (2^-50 ||A||_F)^2. At most max_sweeps sweeps run
+ * whatever the data; a matrix that holds a NaN or an infinity runs all of them and gives NaN eigenvalues (and vectors)
+ * with converged = 0. Squares of the entries must be representable. Workspace: only with vecs.
+ * M2D_ERR_ARG: P <= 0, D outside [1, max_dim]; M2D_ERR_WORKSPACE: ws too small. */
+size_t m2d_sym_eig_workspace_bytes(int P, int D, int vectors);
+int m2d_sym_eig(const double* A, int P, int D, double* w, double* vecs, double* info, void* ws, size_t ws_bytes,
+                void* stream);
+/* Frechet distance of P pairs of Gaussians: mean1, mean2 (P, D), cov1, cov2 (P, D, D) -> out (P, 6):
+ *   [fd, |mean1 - mean2|^2, tr cov1 + tr cov2, tr (cov1 cov2)^1/2, sweeps (the larger of the two solves), converged],
+ *   fd = (|mean1 - mean2|^2 + tr cov1 + tr cov2) - 2 tr (cov1 cov2)^1/2, NOT clipped at zero;
+ *   tr (cov1 cov2)^1/2 = sum_i sqrt(max(l_i, 0)), l the eigenvalues of cov1^1/2 cov2 cov1^1/2, taken in the eigenbasis
+ *   of cov1 = V L V^T, where that matrix is max(L, 0)^1/2 (V^T cov2 V) max(L, 0)^1/2.
+ * Five launches on `stream` (m2d_sym_eig's kernel twice, two products, the sums), no host synchronisation, no other
+ * library. M2D_ERR_ARG: P outside [1, 65535], D outside [1, max_dim]; M2D_ERR_WORKSPACE: ws too small. */
+size_t m2d_frechet_workspace_bytes(int P, int D);
+int m2d_frechet(const double* mean1, const double* cov1, const double* mean2, const double* cov2, int P, int D,
+                double* out, void* ws, size_t ws_bytes, void* stream);
+/* X (G K, D) fp32, rows ldx floats apart, G groups of K consecutive rows -> out[g] = the mean over the K (K - 1) / 2 pairs
+ * i < j of group g of sqrt(sum_d (x_i[d] - x_j[d])^2): the difference in fp32, squares and sums in fp64 (ascending d; the
+ * pairs of a row i over 256 interleaved partial sums and a tree, then the rows likewise). K = 1: NaN. A group's value
+ * does not depend on G. M2D_ERR_ARG: G, K or D <= 0, G > 65535, ldx < D; M2D_ERR_WORKSPACE: ws too small. */
+size_t m2d_pairwise_mean_dist_workspace_bytes(int G, int K);
+int m2d_pairwise_mean_dist(const float* X, long long ldx, int G, int K, int D, double* out, void* ws, size_t ws_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,16 @@ SIGNATURES = {
     "m2d_motion_speed": (_I, [_F, _I, _I, _I, _F, _F]),
     "m2d_beat_align_max_frames": (_I, []),
     "m2d_beat_align": (_I, [_F, _F, _I, _I, _c.c_double, _c.c_double, _c.c_double, _F, _F, _F, _F, _F, _F]),
+    "m2d_kinetic_features": (_I, [_F, _I, _I, _I, _c.c_double, _I, _F, _F]),
+    "m2d_sym_eig_max_dim": (_I, []),
+    "m2d_sym_eig_max_sweeps": (_I, []),
+    "m2d_feature_moments": (_I, [_F, _c.c_longlong, _I, _I, _F, _F, _F]),
+    "m2d_sym_eig_workspace_bytes": (_S, [_I, _I, _I]),
+    "m2d_sym_eig": (_I, [_F, _I, _I, _F, _F, _F, _F, _S, _F]),
+    "m2d_frechet_workspace_bytes": (_S, [_I, _I]),
+    "m2d_frechet": (_I, [_F, _F, _F, _F, _I, _I, _F, _F, _S, _F]),
+    "m2d_pairwise_mean_dist_workspace_bytes": (_S, [_I, _I]),
+    "m2d_pairwise_mean_dist": (_I, [_F, _c.c_longlong, _I, _I, _I, _F, _F, _S, _F]),
 }
 
 _lib = None

@@ -1214,6 +1214,95 @@ class HipKernels:
                 float(sigma_align), _ptr(scores), *[_ptr(t) for t in extra])
         return (scores,) + extra if return_events else scores
 
+    # ---------------------------------------------------------------- distribution scores (metrics.py)
+    @staticmethod
+    def _chk64(what, *tensors):
+        """contiguous fp64 tensors on one HIP device (the moments, matrices and scores of the distribution kernels)"""
+        dev = None
+        for t in tensors:
+            if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+                raise _lib.M2dError("%s: contiguous float64 tensors on a HIP device expected (got %s on %s)"
+                                    % (what, t.dtype, t.device))
+            if dev is not None and t.device != dev:
+                raise _lib.M2dError("%s: tensors on different devices" % what)
+            dev = t.device
+        return dev
+
+    @staticmethod
+    def _rows2d(what, X):
+        """X (N, D) fp32 on a HIP device, unit stride inside a row (a column block of a wider buffer is taken as it
+        is) -> (device, row stride)"""
+        if not X.is_cuda or X.dtype != torch.float32 or X.dim() != 2:
+            raise _lib.M2dError("%s: a 2-D fp32 tensor on a HIP device expected (got %s %s on %s)"
+                                % (what, tuple(X.shape), X.dtype, X.device))
+        if X.shape[1] > 0 and X.stride(1) != 1 or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
+            raise _lib.M2dError("%s: rows must be dense" % what)
+        return X.device, (X.stride(0) if X.shape[0] > 1 else max(X.shape[1], 1))
+
+    def sym_eig_max_dim(self):
+        return _lib.lib().m2d_sym_eig_max_dim()
+
+    def kinetic_features(self, poses, fps=25.0, up_axis=1):
+        """poses (B, T, J, 3), T >= 3 -> F (B, 3 J): per joint the mean squared horizontal speed, the mean squared
+        vertical speed and the mean absolute acceleration (m2d_kinetic_features)"""
+        dev = _chk(poses)
+        if poses.dim() != 4 or poses.shape[3] != 3 or poses.shape[0] == 0 or poses.shape[2] == 0:
+            raise _lib.M2dError("kinetic_features: poses (B, T, J, 3) expected, got %s" % (tuple(poses.shape),))
+        B, T, J, _ = poses.shape
+        F = torch.empty((B, 3 * J), dtype=torch.float32, device=dev)
+        _launch("m2d_kinetic_features", dev, _ptr(poses), B, T, J, float(fps), int(up_axis), _ptr(F))
+        return F
+
+    def feature_moments(self, X):
+        """X (N, D) fp32, N >= 2, D <= sym_eig_max_dim() -> (mean (D), cov (D, D)) fp64, unbiased (m2d_feature_moments)"""
+        dev, ldx = self._rows2d("feature_moments", X)
+        N, D = X.shape
+        mean = torch.empty((D,), dtype=torch.float64, device=dev)
+        cov = torch.empty((D, D), dtype=torch.float64, device=dev)
+        _launch("m2d_feature_moments", dev, _ptr(X), ldx, N, D, _ptr(mean), _ptr(cov))
+        return mean, cov
+
+    def sym_eig(self, A, vectors=False):
+        """A (P, D, D) fp64 symmetric -> (w (P, D) ascending, V (P, D, D) with the eigenvectors as columns or None,
+        info (P, 2) = [sweeps, converged]) (m2d_sym_eig)"""
+        dev = self._chk64("sym_eig", A)
+        if A.dim() != 3 or A.shape[1] != A.shape[2] or A.shape[0] == 0:
+            raise _lib.M2dError("sym_eig: matrices (P, D, D) expected, got %s" % (tuple(A.shape),))
+        P, D, _ = A.shape
+        w = torch.empty((P, D), dtype=torch.float64, device=dev)
+        V = torch.empty((P, D, D), dtype=torch.float64, device=dev) if vectors else None
+        info = torch.empty((P, 2), dtype=torch.float64, device=dev)
+        ws, nws = _workspace(dev, "m2d_sym_eig_workspace_bytes", P, D, int(bool(vectors)))
+        _launch("m2d_sym_eig", dev, _ptr(A), P, D, _ptr(w), _ptr(V), _ptr(info), _ptr(ws), nws)
+        return w, V, info
+
+    def frechet(self, mean1, cov1, mean2, cov2):
+        """P pairs of moments, mean (P, D) and cov (P, D, D) fp64 -> (P, 6) fp64 = [fd, |mean1 - mean2|^2,
+        tr cov1 + tr cov2, tr (cov1 cov2)^1/2, sweeps, converged] (m2d_frechet)"""
+        dev = self._chk64("frechet", mean1, cov1, mean2, cov2)
+        if (mean1.dim() != 2 or mean1.shape[0] == 0 or mean2.shape != mean1.shape
+                or tuple(cov1.shape) != tuple(mean1.shape) + (mean1.shape[1],) or cov2.shape != cov1.shape):
+            raise _lib.M2dError("frechet: means (P, D) and covariances (P, D, D) expected, got %s %s %s %s"
+                                % tuple(tuple(t.shape) for t in (mean1, cov1, mean2, cov2)))
+        P, D = mean1.shape
+        out = torch.empty((P, 6), dtype=torch.float64, device=dev)
+        ws, nws = _workspace(dev, "m2d_frechet_workspace_bytes", P, min(D, self.sym_eig_max_dim()))
+        _launch("m2d_frechet", dev, _ptr(mean1), _ptr(cov1), _ptr(mean2), _ptr(cov2), P, D, _ptr(out), _ptr(ws), nws)
+        return out
+
+    def pairwise_mean_dist(self, X, groups=1):
+        """X (G K, D) fp32, G groups of K consecutive rows -> (G,) fp64: the mean Euclidean distance over the pairs of
+        each group, NaN for K = 1 (m2d_pairwise_mean_dist)"""
+        dev, ldx = self._rows2d("pairwise_mean_dist", X)
+        G = int(groups)
+        if G <= 0 or X.shape[0] == 0 or X.shape[0] % G:
+            raise _lib.M2dError("pairwise_mean_dist: %d rows do not make %d groups" % (X.shape[0], G))
+        K, D = X.shape[0] // G, X.shape[1]
+        out = torch.empty((G,), dtype=torch.float64, device=dev)
+        ws, nws = _workspace(dev, "m2d_pairwise_mean_dist_workspace_bytes", G, K)
+        _launch("m2d_pairwise_mean_dist", dev, _ptr(X), ldx, G, K, D, _ptr(out), _ptr(ws), nws)
+        return out
+
     def dropout(self, x, mask, p_keep=0.5, scale=2.0, seed=None, offset=0, out=None):
         """y = x * keep * scale. seed None: keep from the uint8 `mask` (the caller's); else Philox4x32-10 bits of
         (seed, offset, index), written into `mask` when given. x None: the mask only. -> y (or mask)."""

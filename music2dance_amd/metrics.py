@@ -12,6 +12,16 @@ of a dance - local minima of the body's speed - fall on musical onsets, as the b
 Pose frame t belongs to samples [t hop, (t + 1) hop); STFT frame t is centred on the middle of that interval. Device
 tensors in, device tensors out, no host synchronisation inside. The window, the mel bands, the smoothing widths and
 gamma are conventions of this project (the reference has no such metric); all are parameters.
+
+Distribution scores (include/m2d.h "distribution scores") ask whether a SET of generated dances
+has the distribution of the real ones, as the FID_k / Div_k of AIST++ and the FID, diversity and multimodality of
+"Dancing to Music" do:
+
+    poses    -> kinetic features per joint (m2d_kinetic_features)
+    features -> fp64 mean and covariance (m2d_feature_moments)
+    moments  -> Frechet distance (m2d_frechet: two Jacobi eigen-solves, m2d_sym_eig's kernel, and two products)
+    features -> mean pairwise distance (m2d_pairwise_mean_dist): diversity (one group), multimodality (a group per
+                piece of music)
 """
 import numpy as np
 import torch
@@ -132,3 +142,66 @@ def beat_scores(audio, poses, hop, rate=16000, n_fft=1024, bands=None, gamma=1.0
         raise ValueError("beat_scores: %d audio rows for %d dances" % (x.shape[0], p.shape[0]))
     onset = onset_strength(x, p.shape[1], hop, n_fft, bands, rate, gamma)
     return beat_alignment(onset, motion_speed(p), **kw)
+
+
+# ------------------------------------------------------------------------------------------- distribution scores
+def kinetic_features(poses, fps=25.0, up_axis=1):
+    """poses (B, T, J, 3) or (B, T, 3 J) (one dance: (T, J, 3) or (T, 3 J)) in world units, T >= 3 -> F (B, 3 J) fp32,
+    [h_0 .. h_{J-1} | v_0 .. | e_0 ..]: per joint the mean squared horizontal speed (the two axes other than
+    `up_axis`), the mean squared vertical speed and the mean absolute acceleration, with v[t] = (p[t] - p[t - 1]) fps
+    and a[t] = (p[t + 1] - 2 p[t] + p[t - 1]) fps^2"""
+    return kernels.impl().kinetic_features(_pose_rows(poses), float(fps), int(up_axis))
+
+
+def feature_moments(X):
+    """X (N, D) fp32, N >= 2 -> (mean (D), cov (D, D)) fp64, cov unbiased (N - 1) and exactly symmetric"""
+    return kernels.impl().feature_moments(X)
+
+
+def sym_eig(A, vectors=False):
+    """A (D, D) or (P, D, D) fp64 symmetric -> {'values' (.., D) ascending, 'sweeps', 'converged' (..,)} and, with
+    `vectors`, 'vectors' (.., D, D): the eigenvectors as columns. A matrix with a NaN or an infinity gives NaN values
+    and converged 0 after the solver's fixed number of sweeps."""
+    A3 = A.unsqueeze(0) if A.dim() == 2 else A
+    w, V, info = kernels.impl().sym_eig(A3.contiguous(), vectors)
+    lead = A.shape[:-2]
+    res = {"values": w.reshape(lead + w.shape[-1:]), "sweeps": info[:, 0].reshape(lead),
+           "converged": info[:, 1].reshape(lead)}
+    if vectors:
+        res["vectors"] = V.reshape(A.shape)
+    return res
+
+
+FRECHET_FIELDS = ("fd", "mean_term", "trace_term", "sqrt_term", "sweeps", "converged")
+
+
+def frechet_from_moments(m1, S1, m2, S2):
+    """means (D) / (P, D) and covariances (D, D) / (P, D, D), fp64 -> {'fd', 'mean_term', 'trace_term', 'sqrt_term',
+    'sweeps', 'converged'}, 0-dim (or (P,)) fp64 tensors: fd = mean_term + trace_term - 2 sqrt_term with mean_term =
+    |m1 - m2|^2, trace_term = tr S1 + tr S2, sqrt_term = tr (S1 S2)^1/2. fd is NOT clipped at zero: two equal samples
+    may give a tiny negative number. All pairs of a call go through one m2d_frechet launch sequence."""
+    single = m1.dim() == 1
+    args = [t.unsqueeze(0) if single else t for t in (m1, S1, m2, S2)]
+    out = kernels.impl().frechet(*[t.contiguous() for t in args])
+    return {k: (out[0, i] if single else out[:, i]) for i, k in enumerate(FRECHET_FIELDS)}
+
+
+def frechet_distance(X1, X2):
+    """X1 (N1, D), X2 (N2, D) fp32 feature rows -> frechet_from_moments of their moments"""
+    m1, S1 = feature_moments(X1)
+    m2, S2 = feature_moments(X2)
+    return frechet_from_moments(m1, S1, m2, S2)
+
+
+def mean_pairwise_distance(X, groups=1):
+    """X (G K, D) fp32, `groups` = G groups of K consecutive rows -> (G,) fp64: the mean Euclidean distance over the
+    K (K - 1) / 2 pairs of each group; NaN for K = 1. Diversity is groups = 1; multimodality is the mean over the
+    groups when a group holds the dances made for one piece of music."""
+    return kernels.impl().pairwise_mean_dist(X, int(groups))
+
+
+def standardize(X, mean, cov):
+    """(x - mean) / sqrt(diag cov) per column, fp32; a column whose variance is 0 is divided by 1"""
+    var = torch.diagonal(cov)
+    sd = torch.where(var > 0, var.sqrt(), torch.ones_like(var))
+    return ((X.double() - mean) / sd).float().contiguous()

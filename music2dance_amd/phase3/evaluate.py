@@ -1,7 +1,8 @@
 """Score a trained phase-3 generator as the reference's phase3/test.py:76-140 does, on the HIP path.
 
     python -m music2dance_amd.phase3.evaluate -c music2dance_amd/phase3/configs/default.yaml -l <logdir> \
-        --classifier logs/type2/weights.pt [--gen-weights PATH] [--repeats 20] [--synthetic] [--beat-align]
+        --classifier logs/type2/weights.pt [--gen-weights PATH] [--repeats 20] [--synthetic] [--beat-align] \
+        [--frechet [--modes K]]
 
 1. Jerkiness (losses.jerkiness) of every real validation take and of the dance generated from its music, on
    inverse-MinMax-scaled poses: mean and unbiased standard deviation of each.
@@ -21,6 +22,14 @@ its generated counterpart against the draw's own audio row: `beat_align_{real,fa
 `beat_cover_{real,fake}_{mean,std}` over the rows whose score is defined (a row without a kinematic beat or without an
 onset has none) and `beat_defined_{real,fake}`, the number of such rows. Without the flag evaluation.json is what it
 was.
+
+--frechet adds the distribution scores of DESIGN.md section 14 on the kinetic features (metrics.kinetic_features at the
+config's video_rate) of the inverse-scaled real and generated draws, both standardised by the REAL set's moments:
+`fd_kinetic` (Frechet distance real against generated), `fd_kinetic_real_split` (even against odd real rows: the
+sampling floor `fd_kinetic` is to be read against), `div_kinetic_real`, `div_kinetic_fake` (mean pairwise distance),
+`fd_kinetic_converged` and `kinetic_dims`. --modes K (K >= 2, needs --frechet) runs the generator K times on the same
+audio slices, fresh noise each time, and adds `multimodality_kinetic`: the mean pairwise distance among the K dances
+of a slice, averaged over the slices. A value that needs more rows than there are is `null`.
 """
 import argparse
 import glob
@@ -52,7 +61,16 @@ def parse_args(argv=None):
     ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
     ap.add_argument("--beat-align", action="store_true", help="also score the beat alignment of the real and the "
                                                               "generated dances with their music")
-    return ap.parse_args(argv)
+    ap.add_argument("--frechet", action="store_true", help="also score the Frechet distance and the diversity of the "
+                                                           "kinetic features of the real and the generated dances")
+    ap.add_argument("--modes", type=int, default=None, help="with --frechet: generate K >= 2 dances per audio slice "
+                                                            "and score their multimodality")
+    opts = ap.parse_args(argv)
+    if opts.modes is not None and not opts.frechet:
+        ap.error("--modes requires --frechet")
+    if opts.modes is not None and opts.modes < 2:
+        ap.error("--modes needs K >= 2")
+    return opts
 
 
 def latest_checkpoint(logdir):
@@ -109,8 +127,45 @@ def beat_rows(audio, real_i, fake_i, hop, rate):
     return out
 
 
-def summary(real_jerk, fake_jerk, real_pred, fake_pred, n_classes=N_STYLES, beat=None):
-    """beat: beat_rows' result, or None (the keys of --beat-align are then absent)"""
+def kinetic_rows(real_i, fakes_i, fps, up_axis=1):
+    """The keys of --frechet (and, for more than one generated set, of --modes): real_i (N, T, 69) and the list fakes_i
+    of generated sets of the same shape, inverse-scaled; set k row n is the k-th dance made for the music of real row
+    n. Features are standardised by the real set's moments; both Frechet pairs go through ONE m2d_frechet call. The
+    only host reads are the final scalars."""
+    from .. import metrics
+    nan = float("nan")
+    N = real_i.shape[0]
+    Fr = metrics.kinetic_features(real_i.contiguous(), fps, up_axis)
+    Ff = [metrics.kinetic_features(f.contiguous(), fps, up_axis) for f in fakes_i]
+    res = {"fd_kinetic": nan, "fd_kinetic_real_split": nan, "div_kinetic_real": nan, "div_kinetic_fake": nan,
+           "fd_kinetic_converged": None, "kinetic_dims": int(Fr.shape[1])}
+    if len(fakes_i) > 1:
+        res["multimodality_kinetic"] = nan
+    if N < 2:
+        return res
+    mean, cov = metrics.feature_moments(Fr)
+    Zr = metrics.standardize(Fr, mean, cov)
+    Zf = [metrics.standardize(f, mean, cov) for f in Ff]
+    pairs = [(Zr, Zf[0])] + ([(Zr[0::2], Zr[1::2])] if N >= 4 else [])
+    mom = [[metrics.feature_moments(x) for x in pair] for pair in pairs]
+    fd = metrics.frechet_from_moments(torch.stack([m[0][0] for m in mom]), torch.stack([m[0][1] for m in mom]),
+                                      torch.stack([m[1][0] for m in mom]), torch.stack([m[1][1] for m in mom]))
+    vals = fd["fd"].cpu().numpy()
+    res["fd_kinetic"] = float(vals[0])
+    if len(pairs) > 1:
+        res["fd_kinetic_real_split"] = float(vals[1])
+    res["fd_kinetic_converged"] = bool((fd["converged"] != 0).all().cpu())
+    res["div_kinetic_real"] = float(metrics.mean_pairwise_distance(Zr)[0].cpu())
+    res["div_kinetic_fake"] = float(metrics.mean_pairwise_distance(Zf[0])[0].cpu())
+    if len(Zf) > 1:
+        Z = torch.stack(Zf, 1).reshape(N * len(Zf), -1).contiguous()       # the dances of a slice are consecutive rows
+        res["multimodality_kinetic"] = float(metrics.mean_pairwise_distance(Z, groups=N).mean().cpu())
+    return res
+
+
+def summary(real_jerk, fake_jerk, real_pred, fake_pred, n_classes=N_STYLES, beat=None, kinetic=None):
+    """beat: beat_rows' result, or None (the keys of --beat-align are then absent); kinetic: kinetic_rows' result, or
+    None (the keys of --frechet are then absent)"""
     cm, counts = confusion(real_pred, fake_pred, n_classes)
     rm, rs = jerk_stats(real_jerk)
     fm, fs = jerk_stats(fake_jerk)
@@ -121,6 +176,8 @@ def summary(real_jerk, fake_jerk, real_pred, fake_pred, n_classes=N_STYLES, beat
     if beat is not None:
         for tag in ("real", "fake"):
             res.update(beat_stats(beat[tag][0], beat[tag][1], tag))
+    if kinetic is not None:
+        res.update(kinetic)
     return res
 
 
@@ -213,8 +270,15 @@ def evaluate(opts, cfg, device):
     beat = None
     if getattr(opts, "beat_align", False):
         beat = beat_rows(audio.contiguous(), real_i, fake_i, hop, int(cfg["dataset"]["audio_rate"]))
+    kinetic = None
+    if getattr(opts, "frechet", False):
+        # --modes K: K - 1 further generator calls on the same slices (each draws its own noise), after everything
+        # the scores above are made of
+        more = [scaler.inverse_transform_device(gen(slices, [T] * N).reshape(N, T, STICK_CHANNELS).contiguous())
+                for _ in range((getattr(opts, "modes", None) or 1) - 1)]
+        kinetic = kinetic_rows(real_i, [fake_i] + more, float(cfg["dataset"]["video_rate"]))
     return summary(real_jerk.cpu().numpy(), fake_jerk.cpu().numpy(), real_pred.cpu().numpy(),
-                   fake_pred.cpu().numpy(), beat=beat)
+                   fake_pred.cpu().numpy(), beat=beat, kinetic=kinetic)
 
 
 def main(argv=None):
