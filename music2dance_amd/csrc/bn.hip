@@ -57,6 +57,8 @@ struct BnReduceArgs {
   float eps, momentum;
 };
 
+// (mean / variance / invstd / running update: stated four times, on purpose - bn_finish, m2d_bn_finalize_fwd_kernel,
+// bn_mean_invstd, bn_finalize_side; a change to one is a change to all four)
 // (the launches on ONE stream share a scratch; two streams need two)
 __device__ __forceinline__ void bn_finish(const BnReduceArgs& a, int c, double s0, double s1) {
   if (a.fin == 1) {
@@ -304,6 +306,8 @@ static int launch_reduce(BnReduceArgs& a, hipStream_t stream) {
 }
 
 // ---- finalize kernels (one thread per channel) ---------------------------------
+// (mean / variance / invstd / running update: stated four times, on purpose - bn_finish, m2d_bn_finalize_fwd_kernel,
+// bn_mean_invstd, bn_finalize_side; a change to one is a change to all four)
 __global__ void m2d_bn_finalize_fwd_kernel(const double* acc, float* mean, float* invstd,
                                            float* running_mean, float* running_var, int C, double count,
                                            float eps, float momentum) {
@@ -376,6 +380,8 @@ struct BnApplyArgs {
   float* fin_running_var;
 };
 
+// (mean / variance / invstd / running update: stated four times, on purpose - bn_finish, m2d_bn_finalize_fwd_kernel,
+// bn_mean_invstd, bn_finalize_side; a change to one is a change to all four)
 // mean / invstd of channel c: from the arrays, or from the batch sums (see BnApplyArgs::fin_sums)
 __device__ __forceinline__ void bn_mean_invstd(const BnApplyArgs& a, int c, float& mu, float& is) {
   if (a.fin_sums) {
@@ -389,6 +395,8 @@ __device__ __forceinline__ void bn_mean_invstd(const BnApplyArgs& a, int c, floa
     is = a.invstd[c];
   }
 }
+// (mean / variance / invstd / running update: stated four times, on purpose - bn_finish, m2d_bn_finalize_fwd_kernel,
+// bn_mean_invstd, bn_finalize_side; a change to one is a change to all four)
 // workgroup (0, 0): save_mean / save_invstd and the running buffers (what m2d_bn_finalize_fwd_kernel leaves behind)
 __device__ __forceinline__ void bn_finalize_side(const BnApplyArgs& a) {
   if (!a.fin_sums || blockIdx.x != 0 || blockIdx.y != 0) return;
@@ -628,15 +636,16 @@ extern "C" {
 
 // bytes of scratch every bn / channel-sum call needs (fp64 accumulators + 2 float rows)
 size_t m2d_bn_workspace_bytes(int C) { return (size_t)C * (2 * sizeof(double) + 2 * sizeof(float)) + 64; }
+// the two float rows: the backward's s_dz = sum(dz) / count and s_dzx = sum(dz * xhat) / count
+static inline void bn_bwd_rows(void* ws, int C, float*& s_dz, float*& s_dzx) {
+  s_dz = (float*)((double*)ws + 2 * (size_t)C);
+  s_dzx = s_dz + C;
+}
 
 // bytes of the optional zero-kept scratch (`scratch` arguments below): fp64 accumulators + the arrival counter. The
 // caller zeroes it ONCE; every call that takes it leaves it zeroed. One scratch per stream (launches of one stream
 // reuse it in order); with scratch == NULL the calls memset their accumulators and finalise in a second launch.
 size_t m2d_bn_scratch_bytes(int C) { return (size_t)C * 2 * sizeof(double) + 64; }
-static inline void bn_use_scratch(BnReduceArgs& r, void* scratch, int C) {
-  r.acc = (double*)scratch;
-  r.ticket = (unsigned*)((double*)scratch + 2 * (size_t)C);
-}
 
 static int bn_check(const char* who, int B, int C, int L) {
   if (B <= 0 || C <= 0 || L <= 0) M2D_FAIL(M2D_ERR_ARG, "%s: bad shape", who);
@@ -644,51 +653,92 @@ static int bn_check(const char* who, int B, int C, int L) {
   return M2D_OK;
 }
 
-static int bn_apply_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const float* save_mean,
-                        const float* save_invstd, const float* s_dz, const float* s_dzx, float* dx, int B, int C, int L,
-                        int act, float slope, hipStream_t stream);
+// ---- the two argument blocks: every entry point below builds its kernel arguments here ------------------------------
+// A reduction of `mode` over x (B, C, L). The caller adds the mode's other inputs and says where the sums go: `acc`
+// (stateless: launch_reduce zeroes it, a second launch finishes the op) or bn_use_scratch.
+static BnReduceArgs bn_reduce_args(int mode, const float* x, int B, int C, int L) {
+  BnReduceArgs r;
+  memset(&r, 0, sizeof(r));
+  r.mode = mode;
+  r.x = x;
+  r.B = B; r.C = C; r.L = L;
+  return r;
+}
+// The sums accumulate in the zero-kept scratch and the last block finishes the op as `fin` says (BnReduceArgs::fin;
+// the caller sets the outputs that fin names).
+static void bn_use_scratch(BnReduceArgs& r, void* scratch, int fin) {
+  r.acc = (double*)scratch;
+  r.ticket = (unsigned*)((double*)scratch + 2 * (size_t)r.C);
+  r.fin = fin;
+}
+// A normalisation of x (B, C, L) into a dense `out`, forward; the callers add what is theirs (residual, dy, pitch, ...)
+static BnApplyArgs bn_apply_args(const float* x, const float* gamma, const float* beta, const float* mean,
+                                 const float* invstd, float* out, int C, int L, int act, float slope) {
+  BnApplyArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x;
+  a.gamma = gamma; a.beta = beta;
+  a.mean = mean; a.invstd = invstd;
+  a.out = out;
+  a.C = C; a.L = L; a.L_inv = 1.f / (float)L;
+  a.row_len = C * L;
+  a.act = act; a.slope = slope;
+  return a;
+}
 
-// the finalisation of the batch statistics folded into a normalisation launch (BnApplyArgs::fin_sums)
-struct BnFin {
-  const double* sums;
-  double count;
-  float eps, momentum;
-  float* running_mean;
-  float* running_var;
-};
 static bool bn_fin_in_apply() {   // A/B lever (0: the separate m2d_bn_finalize_fwd_kernel launch of rounds 1-5)
   static const bool on = [] { const char* e = getenv("M2D_BN_FIN_IN_APPLY"); return !(e && e[0] == '0'); }();
   return on;
 }
-static void bn_set_fin(BnApplyArgs& a, const BnFin* fin) {
-  if (!fin) return;
-  a.fin_sums = fin->sums;
-  a.fin_count = fin->count;
-  a.fin_eps = fin->eps;
-  a.fin_momentum = fin->momentum;
-  a.fin_running_mean = fin->running_mean;
-  a.fin_running_var = fin->running_var;
-}
 
+// the forward normalisation launch; residual / pool_out / out_pitch are the caller's to set
+static int bn_launch_fwd(BnApplyArgs& a, int B, hipStream_t stream) {
+  M2dProfScope prof(M2D_FAM_BN, stream, 0.0, ((a.residual ? 3.0 : 2.0) + (a.pool_out ? 0.5 : 0.0)) * 4.0 * B * a.C * (double)a.L,
+                    a.pool_out ? "bn_apply_pool" : "bn_apply", B, a.C, a.L);
+  return launch_apply(a, B, stream);
+}
 static int bn_apply_fwd(const float* x, const float* gamma, const float* beta, const float* mean, const float* invstd,
                         float* y, int B, int C, int L, int act, float slope, const float* residual, hipStream_t stream,
-                        long long y_batch_stride = 0, const BnFin* fin = nullptr, float* pool_out = nullptr) {
-  BnApplyArgs a;
-  memset(&a, 0, sizeof(a));
-  bn_set_fin(a, fin);
-  a.pool_out = pool_out;
-  a.out_pitch = y_batch_stride;
-  a.x = x;
+                        long long y_batch_stride) {
+  BnApplyArgs a = bn_apply_args(x, gamma, beta, mean, invstd, y, C, L, act, slope);
   a.residual = residual;
-  a.gamma = gamma; a.beta = beta;
-  a.mean = mean; a.invstd = invstd;
-  a.out = y;
-  a.C = C; a.L = L; a.L_inv = 1.f / (float)L;
-  a.row_len = C * L;
-  a.act = act; a.slope = slope;
-  M2dProfScope prof(M2D_FAM_BN, stream, 0.0, ((residual ? 3.0 : 2.0) + (pool_out ? 0.5 : 0.0)) * 4.0 * B * C * (double)L,
-                    pool_out ? "bn_apply_pool" : "bn_apply", B, C, L);
+  a.out_pitch = y_batch_stride;
+  return bn_launch_fwd(a, B, stream);
+}
+
+static int bn_apply_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const float* save_mean,
+                        const float* save_invstd, const float* s_dz, const float* s_dzx, float* dx, int B, int C, int L,
+                        int act, float slope, hipStream_t stream) {
+  BnApplyArgs a = bn_apply_args(x, gamma, beta, save_mean, save_invstd, dx, C, L, act, slope);
+  a.dy = dy;
+  a.s_dz = s_dz; a.s_dzx = s_dzx;
+  a.backward = 1;
+  M2dProfScope prof(M2D_FAM_BN, stream, 0.0, 3.0 * 4.0 * B * C * (double)L, "bn_bwd_apply", B, C, L);
   return launch_apply(a, B, stream);
+}
+
+// The head of the three training forwards from batch sums -> `a`, the arguments of their normalisation launch. The checks:
+// shape and statistics under the entry point's name `who`, then `complaint`, what the entry point itself found wrong with
+// its arguments (NULL: nothing). Then THE decision where mean / invstd / the running buffers are made: inside that launch
+// (BnApplyArgs::fin_sums; `apply_finalises`: its kernel can) or by m2d_bn_finalize_fwd_kernel, launched here.
+static int bn_fwd_sums_begin(const char* who, const char* complaint, bool apply_finalises, const float* x,
+                             const double* sums, double count, const float* gamma, const float* beta, float* running_mean,
+                             float* running_var, float* out, float* save_mean, float* save_invstd, int B, int C, int L,
+                             float eps, float momentum, int act, float slope, hipStream_t stream, BnApplyArgs& a) {
+  if (int rc = bn_check(who, B, C, L)) return rc;
+  if (!sums || !(count > 0.0)) M2D_FAIL(M2D_ERR_ARG, "%s: no statistics", who);
+  if (complaint) M2D_FAIL(M2D_ERR_ARG, "%s: %s", who, complaint);
+  a = bn_apply_args(x, gamma, beta, save_mean, save_invstd, out, C, L, act, slope);
+  if (apply_finalises && bn_fin_in_apply()) {   // mean / invstd in every thread's prologue, save_* and the running buffers by workgroup (0, 0)
+    a.fin_sums = sums; a.fin_count = count;
+    a.fin_eps = eps; a.fin_momentum = momentum;
+    a.fin_running_mean = running_mean; a.fin_running_var = running_var;
+    return M2D_OK;
+  }
+  hipLaunchKernelGGL(m2d_bn_finalize_fwd_kernel, dim3(m2d_ceil_div(C, 256)), dim3(256), 0, stream, sums, save_mean,
+                     save_invstd, running_mean, running_var, C, count, eps, momentum);
+  M2D_CHECK_LAUNCH("m2d_bn_finalize_fwd_kernel");
+  return M2D_OK;
 }
 
 // The batch statistics as raw sums: sums[2c] = sum x, sums[2c + 1] = sum x^2 over (batch, length), fp64.
@@ -698,17 +748,12 @@ static int bn_apply_fwd(const float* x, const float* gamma, const float* beta, c
 int m2d_bn_stats(const float* x, double* sums, int B, int C, int L, void* scratch, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (int rc = bn_check("m2d_bn_stats", B, C, L)) return rc;
-  BnReduceArgs r;
-  memset(&r, 0, sizeof(r));
-  r.x = x;
+  BnReduceArgs r = bn_reduce_args(0, x, B, C, L);
   r.acc = sums;
   if (scratch) {
-    bn_use_scratch(r, scratch, C);
-    r.fin = 1;
+    bn_use_scratch(r, scratch, 1);
     r.sums_out = sums;
   }
-  r.B = B; r.C = C; r.L = L;
-  r.mode = 0;
   M2dProfScope prof(M2D_FAM_BN, stream, 0.0, 4.0 * B * C * (double)L, "bn_stats", B, C, L);
   return launch_reduce(r, stream);
 }
@@ -723,16 +768,13 @@ int m2d_bn_fwd_sums_to(const float* x, const double* sums, double count, const f
                        int C, int L, float eps, float momentum, int act, float slope, const float* residual,
                        long long y_batch_stride, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (int rc = bn_check("m2d_bn_fwd_sums", B, C, L)) return rc;
-  if (!sums || !(count > 0.0)) M2D_FAIL(M2D_ERR_ARG, "m2d_bn_fwd_sums: no statistics");
-  if (bn_fin_in_apply()) {   // mean / invstd in every thread's prologue, save_* and the running buffers by workgroup (0, 0)
-    const BnFin fin = {sums, count, eps, momentum, running_mean, running_var};
-    return bn_apply_fwd(x, gamma, beta, save_mean, save_invstd, y, B, C, L, act, slope, residual, stream, y_batch_stride, &fin);
-  }
-  hipLaunchKernelGGL(m2d_bn_finalize_fwd_kernel, dim3(m2d_ceil_div(C, 256)), dim3(256), 0, stream, sums, save_mean,
-                     save_invstd, running_mean, running_var, C, count, eps, momentum);
-  M2D_CHECK_LAUNCH("m2d_bn_finalize_fwd_kernel");
-  return bn_apply_fwd(x, gamma, beta, save_mean, save_invstd, y, B, C, L, act, slope, residual, stream, y_batch_stride);
+  BnApplyArgs a;
+  if (int rc = bn_fwd_sums_begin("m2d_bn_fwd_sums", nullptr, true, x, sums, count, gamma, beta, running_mean, running_var, y,
+                                 save_mean, save_invstd, B, C, L, eps, momentum, act, slope, stream, a))
+    return rc;
+  a.residual = residual;
+  a.out_pitch = y_batch_stride;
+  return bn_launch_fwd(a, B, stream);
 }
 // The running buffers advanced ONCE MORE with batch statistics they have already been advanced with (same fp64 sums ->
 // exactly what a second training-mode forward of the same batch through the same weights would leave behind). The
@@ -770,17 +812,14 @@ int m2d_bn_fwd_sums_pool_to(const float* x, const double* sums, double count, co
                             float* save_invstd, int B, int C, int L, float eps, float momentum, int act, float slope,
                             long long y_batch_stride, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (int rc = bn_check("m2d_bn_fwd_sums_pool_to", B, C, L)) return rc;
-  if (!sums || !(count > 0.0)) M2D_FAIL(M2D_ERR_ARG, "m2d_bn_fwd_sums_pool_to: no statistics");
-  if (!pooled || (L & 1)) M2D_FAIL(M2D_ERR_ARG, "m2d_bn_fwd_sums_pool_to: even L and a pooled output");
-  const BnFin fin = {sums, count, eps, momentum, running_mean, running_var};
-  if (!bn_fin_in_apply()) {
-    hipLaunchKernelGGL(m2d_bn_finalize_fwd_kernel, dim3(m2d_ceil_div(C, 256)), dim3(256), 0, stream, sums, save_mean,
-                       save_invstd, running_mean, running_var, C, count, eps, momentum);
-    M2D_CHECK_LAUNCH("m2d_bn_finalize_fwd_kernel");
-  }
-  return bn_apply_fwd(x, gamma, beta, save_mean, save_invstd, y, B, C, L, act, slope, nullptr, stream, y_batch_stride,
-                      bn_fin_in_apply() ? &fin : nullptr, pooled);
+  BnApplyArgs a;
+  if (int rc = bn_fwd_sums_begin("m2d_bn_fwd_sums_pool_to", (!pooled || (L & 1)) ? "even L and a pooled output" : nullptr,
+                                 true, x, sums, count, gamma, beta, running_mean, running_var, y, save_mean, save_invstd,
+                                 B, C, L, eps, momentum, act, slope, stream, a))
+    return rc;
+  a.pool_out = pooled;
+  a.out_pitch = y_batch_stride;
+  return bn_launch_fwd(a, B, stream);
 }
 
 int m2d_bn_fwd_sums_upsample2_to(const float* x, const double* sums, double count, const float* gamma, const float* beta,
@@ -788,31 +827,16 @@ int m2d_bn_fwd_sums_upsample2_to(const float* x, const double* sums, double coun
                                  int B, int C, int L, float eps, float momentum, int act, float slope,
                                  long long up_batch_stride, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (int rc = bn_check("m2d_bn_fwd_sums_upsample2_to", B, C, L)) return rc;
-  if (!sums || !(count > 0.0)) M2D_FAIL(M2D_ERR_ARG, "m2d_bn_fwd_sums_upsample2_to: no statistics");
   const long long per = (long long)C * L;
   if (up_batch_stride <= 0) up_batch_stride = 2 * per;
-  if ((per & 1) || up_batch_stride < 2 * per || (up_batch_stride & 3) || (((uintptr_t)x | (uintptr_t)up) & 15u))
-    M2D_FAIL(M2D_ERR_ARG, "m2d_bn_fwd_sums_upsample2_to: C * L even, 16-byte aligned samples");
-  const bool rows = (L & 1) == 0;
-  const bool fused_fin = rows && bn_fin_in_apply();   // (the flat form reads the parameters per pair: it keeps the arrays)
-  if (!fused_fin) {
-    hipLaunchKernelGGL(m2d_bn_finalize_fwd_kernel, dim3(m2d_ceil_div(C, 256)), dim3(256), 0, stream, sums, save_mean,
-                       save_invstd, running_mean, running_var, C, count, eps, momentum);
-    M2D_CHECK_LAUNCH("m2d_bn_finalize_fwd_kernel");
-  }
+  const bool misfit = (per & 1) || up_batch_stride < 2 * per || (up_batch_stride & 3) || (((uintptr_t)x | (uintptr_t)up) & 15u);
+  const bool rows = (L & 1) == 0;   // (the flat form reads the parameters per pair: it keeps the arrays)
   BnApplyArgs a;
-  memset(&a, 0, sizeof(a));
-  const BnFin fin = {sums, count, eps, momentum, running_mean, running_var};
-  if (fused_fin) bn_set_fin(a, &fin);
+  if (int rc = bn_fwd_sums_begin("m2d_bn_fwd_sums_upsample2_to", misfit ? "C * L even, 16-byte aligned samples" : nullptr,
+                                 rows, x, sums, count, gamma, beta, running_mean, running_var, up, save_mean, save_invstd,
+                                 B, C, L, eps, momentum, act, slope, stream, a))
+    return rc;
   a.out_pitch = up_batch_stride;
-  a.x = x;
-  a.gamma = gamma; a.beta = beta;
-  a.mean = save_mean; a.invstd = save_invstd;
-  a.out = up;
-  a.C = C; a.L = L; a.L_inv = 1.f / (float)L;
-  a.row_len = C * L;
-  a.act = act; a.slope = slope;
   M2dProfScope prof(M2D_FAM_BN, stream, 0.0, 3.0 * 4.0 * B * C * (double)L, "bn_apply_upsample2", B, C, L);
   if (rows) {
     const int rvl = a.row_len / 2;
@@ -853,15 +877,10 @@ int m2d_bn_fwd_to(const float* x, const float* gamma, const float* beta, float* 
   if (ws_bytes < m2d_bn_workspace_bytes(C) || !ws) M2D_FAIL(M2D_ERR_WORKSPACE, "m2d_bn_fwd: workspace too small");
   if (training && scratch) {
     // statistics + mean / invstd / running buffers in one launch, then the apply pass
-    BnReduceArgs r;
-    memset(&r, 0, sizeof(r));
-    r.x = x;
-    bn_use_scratch(r, scratch, C);
-    r.fin = 2;
+    BnReduceArgs r = bn_reduce_args(0, x, B, C, L);
+    bn_use_scratch(r, scratch, 2);
     r.f0 = save_mean; r.f1 = save_invstd; r.f2 = running_mean; r.f3 = running_mean ? running_var : nullptr;
     r.count = (double)B * L; r.eps = eps; r.momentum = momentum;
-    r.B = B; r.C = C; r.L = L;
-    r.mode = 0;
     {
       M2dProfScope prof(M2D_FAM_BN, stream, 0.0, 4.0 * B * C * (double)L, "bn_stats", B, C, L);
       if (int rc = launch_reduce(r, stream)) return rc;
@@ -894,18 +913,14 @@ int m2d_bn_bwd_stats(const float* dy, const float* x, const float* gamma, const 
                      void* scratch, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (int rc = bn_check("m2d_bn_bwd_stats", B, C, L)) return rc;
-  BnReduceArgs r;
-  memset(&r, 0, sizeof(r));
-  r.x = x; r.dy = dy;
+  BnReduceArgs r = bn_reduce_args(1, x, B, C, L);
+  r.dy = dy; r.act = act; r.slope = slope;
   r.gamma = gamma; r.beta = beta; r.mean = save_mean; r.invstd = save_invstd;
   r.acc = sums;
   if (scratch) {
-    bn_use_scratch(r, scratch, C);
-    r.fin = 1;
+    bn_use_scratch(r, scratch, 1);
     r.sums_out = sums;
   }
-  r.B = B; r.C = C; r.L = L;
-  r.mode = 1; r.act = act; r.slope = slope;
   M2dProfScope prof(M2D_FAM_BN, stream, 0.0, 2.0 * 4.0 * B * C * (double)L, "bn_bwd_reduce", B, C, L);
   return launch_reduce(r, stream);
 }
@@ -921,28 +936,12 @@ int m2d_bn_bwd_sums(const float* dy, const float* x, const float* gamma, const f
   if (int rc = bn_check("m2d_bn_bwd_sums", B, C, L)) return rc;
   if (ws_bytes < m2d_bn_workspace_bytes(C) || !ws) M2D_FAIL(M2D_ERR_WORKSPACE, "m2d_bn_bwd_sums: workspace too small");
   if (!sums_local || !sums_global || !(count > 0.0)) M2D_FAIL(M2D_ERR_ARG, "m2d_bn_bwd_sums: no sums");
-  float* s_dz = (float*)((double*)ws + 2 * (size_t)C);
-  float* s_dzx = s_dz + C;
+  float *s_dz, *s_dzx;
+  bn_bwd_rows(ws, C, s_dz, s_dzx);
   hipLaunchKernelGGL(m2d_bn_finalize_bwd_kernel, dim3(m2d_ceil_div(C, 256)), dim3(256), 0, stream, sums_local,
                      sums_global, dgamma, dbeta, s_dz, s_dzx, C, count);
   M2D_CHECK_LAUNCH("m2d_bn_finalize_bwd_kernel");
   return bn_apply_bwd(dy, x, gamma, beta, save_mean, save_invstd, s_dz, s_dzx, dx, B, C, L, act, slope, stream);
-}
-
-static int bn_apply_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const float* save_mean,
-                        const float* save_invstd, const float* s_dz, const float* s_dzx, float* dx, int B, int C, int L,
-                        int act, float slope, hipStream_t stream) {
-  BnApplyArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.dy = dy;
-  a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
-  a.s_dz = s_dz; a.s_dzx = s_dzx;
-  a.out = dx;
-  a.C = C; a.L = L; a.L_inv = 1.f / (float)L;
-  a.row_len = C * L;
-  a.backward = 1; a.act = act; a.slope = slope;
-  M2dProfScope prof(M2D_FAM_BN, stream, 0.0, 3.0 * 4.0 * B * C * (double)L, "bn_bwd_apply", B, C, L);
-  return launch_apply(a, B, stream);
 }
 
 // Training-mode backward (single process): the two calls above on the workspace.
@@ -953,18 +952,14 @@ int m2d_bn_bwd(const float* dy, const float* x, const float* gamma, const float*
   if (ws_bytes < m2d_bn_workspace_bytes(C) || !ws) M2D_FAIL(M2D_ERR_WORKSPACE, "m2d_bn_bwd: workspace too small");
   if (scratch) {
     hipStream_t stream = (hipStream_t)stream_;
-    float* s_dz = (float*)((double*)ws + 2 * (size_t)C);
-    float* s_dzx = s_dz + C;
-    BnReduceArgs r;
-    memset(&r, 0, sizeof(r));
-    r.x = x; r.dy = dy;
+    float *s_dz, *s_dzx;
+    bn_bwd_rows(ws, C, s_dz, s_dzx);
+    BnReduceArgs r = bn_reduce_args(1, x, B, C, L);
+    r.dy = dy; r.act = act; r.slope = slope;
     r.gamma = gamma; r.beta = beta; r.mean = save_mean; r.invstd = save_invstd;
-    bn_use_scratch(r, scratch, C);
-    r.fin = 3;
+    bn_use_scratch(r, scratch, 3);
     r.f0 = dgamma; r.f1 = dbeta; r.f2 = s_dz; r.f3 = s_dzx;
     r.count = (double)B * L;
-    r.B = B; r.C = C; r.L = L;
-    r.mode = 1; r.act = act; r.slope = slope;
     {
       M2dProfScope prof(M2D_FAM_BN, stream, 0.0, 2.0 * 4.0 * B * C * (double)L, "bn_bwd_reduce", B, C, L);
       if (int rc = launch_reduce(r, stream)) return rc;
@@ -987,17 +982,13 @@ int m2d_channel_sums(const float* x, const float* mask, float slope, float* out,
   if (B <= 0 || C <= 0 || L <= 0) M2D_FAIL(M2D_ERR_ARG, "m2d_channel_sums: bad shape");
   if (!scratch && (ws_bytes < m2d_bn_workspace_bytes(C) || !ws))
     M2D_FAIL(M2D_ERR_WORKSPACE, "m2d_channel_sums: workspace too small");
-  BnReduceArgs r;
-  memset(&r, 0, sizeof(r));
-  r.x = x; r.mask = mask; r.slope = slope;
+  BnReduceArgs r = bn_reduce_args(2, x, B, C, L);
+  r.mask = mask; r.slope = slope;
   r.acc = (double*)ws;
   if (scratch) {
-    bn_use_scratch(r, scratch, C);
-    r.fin = 4;
+    bn_use_scratch(r, scratch, 4);
     r.f0 = out;
   }
-  r.B = B; r.C = C; r.L = L;
-  r.mode = 2;
   M2dProfScope prof(M2D_FAM_REDUCE, stream, 0.0, (mask ? 8.0 : 4.0) * B * C * (double)L, "channel_sums", B, C, L);
   int rc = launch_reduce(r, stream);
   if (rc || scratch) return rc;

@@ -669,13 +669,22 @@ class HipKernels:
         assert out.dim() == 3 and out.stride(2) == 1 and out.stride(1) == out.shape[2] and out.stride(0) >= out.shape[1] * out.shape[2]
         return out, out.stride(0)
 
-    def bn_fwd(self, x, gamma, beta, running_mean, running_var, training, eps, momentum, act=0, slope=0.0,
-               residual=None, out=None):
+    def _bn_fwd_begin(self, x, gamma, beta, running_mean, running_var, residual=None, sums=None, out=None, up=1):
+        """What the BatchNorm forwards share: the tensor checks, the result ((B, C, up * L), placed by `_out_block`) and the
+        two (C,) rows kept for the backward. -> dev, (B, C, L), y, its batch stride, save_mean, save_invstd"""
         dev = _chk(x, gamma, beta, running_mean, running_var, residual)
         B, C, L = _bcl(x)
-        y, ypitch = self._out_block(out, x.shape, dev)
+        if sums is not None:
+            self._sums_ok(sums, C, dev)
+        y, ypitch = self._out_block(out, x.shape if up == 1 else (B, C, up * L), dev)
         save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
         save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+        return dev, (B, C, L), y, ypitch, save_mean, save_invstd
+
+    def bn_fwd(self, x, gamma, beta, running_mean, running_var, training, eps, momentum, act=0, slope=0.0,
+               residual=None, out=None):
+        dev, (B, C, L), y, ypitch, save_mean, save_invstd = self._bn_fwd_begin(x, gamma, beta, running_mean, running_var,
+                                                                              residual, None, out)
         ws, nws = _workspace(dev, 'm2d_bn_workspace_bytes', C)
         _launch("m2d_bn_fwd_to", dev, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(y),
                 _ptr(save_mean), _ptr(save_invstd), B, C, L, eps, momentum, 1 if training else 0, act, slope,
@@ -699,12 +708,8 @@ class HipKernels:
                     residual=None, out=None):
         """Training forward from batch sums over `count` elements per channel (bn_stats, a conv's epilogue, or
         their all-reduce across data-parallel ranks). -> y, save_mean, save_invstd."""
-        dev = _chk(x, gamma, beta, running_mean, running_var, residual)
-        B, C, L = _bcl(x)
-        self._sums_ok(sums, C, dev)
-        y, ypitch = self._out_block(out, x.shape, dev)
-        save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
-        save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+        dev, (B, C, L), y, ypitch, save_mean, save_invstd = self._bn_fwd_begin(x, gamma, beta, running_mean, running_var,
+                                                                              residual, sums, out)
         _launch("m2d_bn_fwd_sums_to", dev, _ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
                 _ptr(running_mean), _ptr(running_var), _ptr(y), _ptr(save_mean), _ptr(save_invstd), B, C, L, eps,
                 momentum, act, slope, _ptr(residual), ypitch)
@@ -723,13 +728,9 @@ class HipKernels:
                          out=None):
         """bn_fwd_sums with MaxPool1d(2, 2) of the result made in the same pass. -> (y, pooled, save_mean, save_invstd);
         out: where y goes (a channel block of a wider buffer, as bn_fwd_sums)."""
-        dev = _chk(x, gamma, beta, running_mean, running_var)
-        B, C, L = x.shape
-        self._sums_ok(sums, C, dev)
-        y, ypitch = self._out_block(out, x.shape, dev)
+        dev, (B, C, L), y, ypitch, save_mean, save_invstd = self._bn_fwd_begin(x, gamma, beta, running_mean, running_var,
+                                                                              None, sums, out)
         pooled = torch.empty((B, C, L // 2), dtype=torch.float32, device=dev)
-        save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
-        save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
         _launch("m2d_bn_fwd_sums_pool_to", dev, _ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
                 _ptr(running_mean), _ptr(running_var), _ptr(y), _ptr(pooled), _ptr(save_mean), _ptr(save_invstd), B, C,
                 L, eps, momentum, act, slope, ypitch)
@@ -739,12 +740,8 @@ class HipKernels:
                               out=None):
         """upsample2_linear(bn_fwd_sums(x)) in one pass (the normalised tensor itself is not written).
         -> (up (B, C, 2L), save_mean, save_invstd); out: a (B, C, 2L) channel block of a wider buffer."""
-        dev = _chk(x, gamma, beta, running_mean, running_var)
-        B, C, L = x.shape
-        self._sums_ok(sums, C, dev)
-        up, pitch = self._out_block(out, (B, C, 2 * L), dev)
-        save_mean = torch.empty((C,), dtype=torch.float32, device=dev)
-        save_invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+        dev, (B, C, L), up, pitch, save_mean, save_invstd = self._bn_fwd_begin(x, gamma, beta, running_mean, running_var,
+                                                                              None, sums, out, up=2)
         _launch("m2d_bn_fwd_sums_upsample2_to", dev, _ptr(x), _ptr(sums), float(count), _ptr(gamma), _ptr(beta),
                 _ptr(running_mean), _ptr(running_var), _ptr(up), _ptr(save_mean), _ptr(save_invstd), B, C, L, eps,
                 momentum, act, slope, pitch)
@@ -759,26 +756,27 @@ class HipKernels:
                 _ptr(save_invstd), _ptr(sums), B, C, L, act, slope, _ptr(_bn_scratch(dev, C)))
         return sums
 
-    def bn_bwd_sums(self, dy, x, gamma, beta, save_mean, save_invstd, sums_local, sums_global, count, act=0, slope=0.0):
+    def _bn_bwd_begin(self, dy, x, gamma, beta, save_mean, save_invstd, *sums):
+        """What the two backwards share: the checks, the three results and the workspace."""
         dev = _chk(dy, x, gamma, beta, save_mean, save_invstd)
         B, C, L = _bcl(x)
-        self._sums_ok(sums_local, C, dev), self._sums_ok(sums_global, C, dev)
+        for s in sums:
+            self._sums_ok(s, C, dev)
         dx = torch.empty_like(x)
         dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
         dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
-        ws, nws = _workspace(dev, 'm2d_bn_workspace_bytes', C)
+        return (dev, (B, C, L), dx, dgamma, dbeta) + _workspace(dev, 'm2d_bn_workspace_bytes', C)
+
+    def bn_bwd_sums(self, dy, x, gamma, beta, save_mean, save_invstd, sums_local, sums_global, count, act=0, slope=0.0):
+        dev, (B, C, L), dx, dgamma, dbeta, ws, nws = self._bn_bwd_begin(dy, x, gamma, beta, save_mean, save_invstd,
+                                                                       sums_local, sums_global)
         _launch("m2d_bn_bwd_sums", dev, _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(save_mean), _ptr(save_invstd),
                 _ptr(sums_local), _ptr(sums_global), float(count), _ptr(dx), _ptr(dgamma), _ptr(dbeta), B, C, L, act,
                 slope, _ptr(ws), nws)
         return dx, dgamma, dbeta
 
     def bn_bwd(self, dy, x, gamma, beta, save_mean, save_invstd, act=0, slope=0.0):
-        dev = _chk(dy, x, gamma, beta, save_mean, save_invstd)
-        B, C, L = _bcl(x)
-        dx = torch.empty_like(x)
-        dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
-        dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
-        ws, nws = _workspace(dev, 'm2d_bn_workspace_bytes', C)
+        dev, (B, C, L), dx, dgamma, dbeta, ws, nws = self._bn_bwd_begin(dy, x, gamma, beta, save_mean, save_invstd)
         _launch("m2d_bn_bwd", dev, _ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(save_mean), _ptr(save_invstd),
                 _ptr(dx), _ptr(dgamma), _ptr(dbeta), B, C, L, act, slope, _ptr(ws), nws, _ptr(_bn_scratch(dev, C)))
         return dx, dgamma, dbeta

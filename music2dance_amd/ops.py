@@ -505,11 +505,7 @@ def _bn_forward(x, gamma, beta, running_mean, running_var, residual, training, e
     if training:
         world = _sync_world()
     kw = {} if out is None else {"out": out}
-    if training and sums is None and world == 1:
-        # one process, no sums handed over: statistics, mean / invstd and the running buffers in one launch
-        y, mean, invstd = K().bn_fwd(x, gamma, beta, running_mean, running_var, True, eps, momentum, act, slope,
-                                     residual, **kw)
-    elif training:
+    if training and (sums is not None or world > 1):
         # batch statistics as raw sums: from the producing conv's epilogue when it supplied them
         if sums is None:
             sums = K().bn_stats(x)
@@ -520,8 +516,9 @@ def _bn_forward(x, gamma, beta, running_mean, running_var, residual, training, e
         y, mean, invstd = K().bn_fwd_sums(x, sums, count, gamma, beta, running_mean, running_var, eps, momentum,
                                           act, slope, residual, **kw)
     else:
-        y, mean, invstd = K().bn_fwd(x, gamma, beta, running_mean, running_var, False, eps, momentum, act,
-                                     slope, residual, **kw)
+        # eval, or one process and no sums handed over: statistics, mean / invstd and the running buffers in one launch
+        y, mean, invstd = K().bn_fwd(x, gamma, beta, running_mean, running_var, bool(training), eps, momentum, act, slope,
+                                     residual, **kw)
     return x, y, mean, invstd, world
 
 

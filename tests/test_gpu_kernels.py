@@ -283,9 +283,7 @@ BN_CASES = [(64, 128, 1), (7680, 256, 1), (48, 32, 64), (48, 1024, 2), (24, 64, 
             (6, 32, 800), (6, 128, 25), (5, 3, 7)]
 
 
-@pytest.mark.parametrize("shape", BN_CASES, ids=lambda c: "x".join(map(str, c)))
-@pytest.mark.parametrize("act", [0, 1, 2])
-def test_bn_train_fwd_bwd(shape, act):
+def _check_bn_train_fwd_bwd(shape, act):
     B, C, L = shape
     x = gen(B, C, L, seed=1) * 1.5 + 0.3
     if L == 1:
@@ -310,6 +308,50 @@ def test_bn_train_fwd_bwd(shape, act):
     dx, dg, db = K().bn_bwd(dy.to(DEV), x.to(DEV), gamma.to(DEV), beta.to(DEV), mean, invstd, act, slope)
     assert rel_err(dx, gx) < 2e-5
     assert rel_err(dg, gg) < 2e-5 and rel_err(db, gb) < 2e-5
+
+
+@pytest.mark.parametrize("shape", BN_CASES, ids=lambda c: "x".join(map(str, c)))
+@pytest.mark.parametrize("act", [0, 1, 2])
+def test_bn_train_fwd_bwd(shape, act):
+    _check_bn_train_fwd_bwd(shape, act)
+
+
+# wider than the fixed zero-kept scratch (kernels._BN_MAX_C): every reducing call takes its stateless form - accumulators
+# zeroed by a memset, a second launch to finish - as it does inside a capture that was given no scratch. One case whose
+# rows are read as vectors, one with L == 1.
+BN_STATELESS_CASES = [(3, 4100, 2), (5, 4100, 1)]
+
+
+@pytest.mark.parametrize("shape", BN_STATELESS_CASES, ids=lambda c: "x".join(map(str, c)))
+@pytest.mark.parametrize("act", [0, 1, 2])
+def test_bn_train_fwd_bwd_without_the_scratch(shape, act):
+    from music2dance_amd import kernels
+    assert shape[1] > kernels._BN_MAX_C and kernels._bn_scratch(torch.device(DEV), shape[1]) is None
+    _check_bn_train_fwd_bwd(shape, act)
+
+
+@pytest.mark.parametrize("shape", BN_STATELESS_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_bn_halves_equal_the_fused_calls_without_the_scratch(shape):
+    """bn_stats + bn_fwd_sums against bn_fwd, bn_bwd_stats + bn_bwd_sums against bn_bwd, all in their stateless forms
+    (the bound of test_conv1d_epilogue_statistics_and_bn_from_sums)."""
+    B, C, L = shape
+    k = K()
+    x = (gen(B, C, L, seed=1) * 1.5 + 0.3).to(DEV)
+    if L == 1:
+        x = x.view(B, C)
+    g, bt = gen(C, seed=5).abs().add(0.5).to(DEV), gen(C, seed=6, scale=0.2).to(DEV)
+    rm1, rv1 = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+    rm2, rv2 = rm1.clone(), rv1.clone()
+    o1, m1, i1 = k.bn_fwd(x, g, bt, rm1, rv1, True, 1e-5, 0.1, act=2, slope=0.2)
+    o2, m2, i2 = k.bn_fwd_sums(x, k.bn_stats(x), B * L, g, bt, rm2, rv2, 1e-5, 0.1, act=2, slope=0.2)
+    for a_, b_ in ((o1, o2), (m1, m2), (i1, i2), (rm1, rm2), (rv1, rv2)):
+        assert rel_err(a_, b_.double()) < 2e-6
+    dy = gen(*x.shape, seed=7).to(DEV)
+    dx1, dg1, db1 = k.bn_bwd(dy, x, g, bt, m1, i1, act=2, slope=0.2)
+    loc = k.bn_bwd_stats(dy, x, g, bt, m1, i1, act=2, slope=0.2)
+    dx2, dg2, db2 = k.bn_bwd_sums(dy, x, g, bt, m1, i1, loc, loc, B * L, act=2, slope=0.2)
+    for a_, b_ in ((dx1, dx2), (dg1, dg2), (db1, db2)):
+        assert rel_err(a_, b_.double()) < 2e-6
 
 
 def test_bn_eval_and_residual():
@@ -1049,3 +1091,63 @@ def test_batchnorm_pass_with_the_following_pool_or_upsampling_fused_in(shape):
         y, p, m3, i3 = k.bn_fwd_sums_pool(x, sums, float(B * L), g, b, rm3, rv3, 1e-5, 0.1, act=2, slope=0.2, out=wide[:, C:])
         assert torch.equal(y, y_ref) and torch.equal(p, k.maxpool2_fwd(y_ref)) and bool((wide[:, :C] == 7.0).all())
         assert torch.equal(m3, m_ref) and torch.equal(i3, i_ref) and torch.equal(rm1, rm3) and torch.equal(rv1, rv3)
+
+
+def _from_sums_forwards():
+    """The three training forwards from batch sums, dense and into a channel block of a wider buffer -> {name: CPU tensor}
+    of every output, save_mean / save_invstd and the running buffers. Shapes of the test above: rows of vectors, the
+    upsampling's flat kernel (odd L), a single row group; the pool form where L is even."""
+    k = K()
+    res = {}
+    for B, C, L in [(9, 16, 200), (7, 6, 3), (4, 6, 25)]:
+        x = gen(B, C, L, seed=1).to(DEV)
+        g, b = gen(C, seed=2).abs().add(0.5).to(DEV), gen(C, seed=3, scale=0.3).to(DEV)
+        x64 = x.double()
+        sums = torch.stack((x64.sum((0, 2)), (x64 * x64).sum((0, 2))), 1).reshape(-1)
+
+        def run(tag, fn, wide=None, block=None):
+            rm, rv = torch.full((C,), 0.25, device=DEV), torch.full((C,), 1.5, device=DEV)
+            kw = {} if wide is None else {"out": wide[:, block]}
+            outs = tuple(fn(x, sums, float(B * L), g, b, rm, rv, 1e-5, 0.1, act=2, slope=0.2, **kw))
+            for i, t in enumerate(outs + (rm, rv) + (() if wide is None else (wide,))):
+                res["%dx%dx%d %s %d" % (B, C, L, tag, i)] = t.cpu()
+
+        run("fwd", k.bn_fwd_sums)
+        run("fwd block", k.bn_fwd_sums, torch.full((B, 2 * C, L), 7.0, device=DEV), slice(C, None))
+        run("upsample", k.bn_fwd_sums_upsample2)
+        run("upsample block", k.bn_fwd_sums_upsample2, torch.full((B, 2 * C, 2 * L), 7.0, device=DEV), slice(None, C))
+        if L % 2 == 0:
+            run("pool", k.bn_fwd_sums_pool)
+            run("pool block", k.bn_fwd_sums_pool, torch.full((B, 2 * C, L), 7.0, device=DEV), slice(C, None))
+    return res
+
+
+def test_from_sums_forwards_with_the_separate_finalize_launch(tmp_path):
+    """M2D_BN_FIN_IN_APPLY=0 (csrc/bn.hip: mean / invstd / running buffers by m2d_bn_finalize_fwd_kernel before the
+    normalisation launch, instead of inside it) gives the same bits as the default. The library reads the variable once,
+    so the other arm runs in a fresh child process."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "separate_finalize.pt")
+    code = ("import sys, torch; sys.path.insert(0, %r); from tests import test_gpu_kernels as t; "
+            "torch.save(t._from_sums_forwards(), %r)" % (root, out))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, M2D_BN_FIN_IN_APPLY="0"), cwd=root,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    theirs = torch.load(out)
+    mine = _from_sums_forwards()
+    assert sorted(mine) == sorted(theirs) and len(mine) == 3 * 22 + 13
+    for name, t in mine.items():
+        assert torch.equal(t, theirs[name]), name
+
+
+def test_bn_fwd_sums_pool_rejects_an_odd_length():
+    from music2dance_amd import _lib
+    B, C, L = 4, 6, 25
+    x = gen(B, C, L, seed=1).to(DEV)
+    sums = torch.ones(2 * C, dtype=torch.float64, device=DEV)
+    g, b, rm, rv = (torch.ones(C, device=DEV) for _ in range(4))
+    with pytest.raises(_lib.M2dError, match="even L and a pooled output"):
+        K().bn_fwd_sums_pool(x, sums, float(B * L), g, b, rm, rv, 1e-5, 0.1, act=2, slope=0.2)
