@@ -663,7 +663,6 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(co
       for (int i = 0; i < GRU_FWD_MAXB; ++i) {
         const int j = wave + NW * i;
         if (j < nblk) {
-          const int k0 = 16 * j + 4 * q;
 #pragma unroll
           for (int m = 0; m < 4; ++m) {
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ai[i][m], bwi[i][m][0], acc[0], 0, 0, 0);
@@ -678,7 +677,6 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(co
       for (int i = 0; i < GRU_FWD_MAXB; ++i) {
         const int j = wave + NW * i;
         if (j < nblk) {
-          const int k0 = 16 * j + 4 * q;
 #pragma unroll
           for (int m = 0; m < 4; ++m) {
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah[i][m], bwh[i][m][0], acc[0], 0, 0, 0);
@@ -868,7 +866,6 @@ __device__ __forceinline__ void gru_bwd_contract(const float* base, size_t row_o
   for (int i = 0; i < GRU_BWD_MAXB; ++i) {
     const int j = wave + NW * i;
     if (j < nblk) {
-      const int k0 = 16 * j + 4 * q;
 #pragma unroll
       for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][m], bw[i][m], acc, 0, 0, 0);
     }
@@ -990,60 +987,59 @@ static GruPersistState g_gru_ps[16];
 static bool g_gru_ps_init[16];
 static std::mutex g_gru_mu;
 
-static GruPersistState* gru_persist_state_peek() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  std::lock_guard<std::mutex> lk(g_gru_mu);
-  return g_gru_ps_init[dev] ? &g_gru_ps[dev] : nullptr;
-}
-
-static GruPersistState* gru_persist_state() {
+// This device's state. With `create` it is set up on first use, and NULL when the persistent form is off
+// (M2D_PERSISTENT_GRU=0) or the set-up failed; without, it is returned as it is, NULL before any set-up.
+static GruPersistState* gru_persist_state(bool create = true) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   std::lock_guard<std::mutex> lk(g_gru_mu);
   GruPersistState& ps = g_gru_ps[dev];
+  if (!create) return g_gru_ps_init[dev] ? &ps : nullptr;
   if (!g_gru_ps_init[dev]) {
     g_gru_ps_init[dev] = true;
     const char* e = getenv("M2D_PERSISTENT_GRU");
-    if (e && e[0] == '0') return &ps;  // usable stays false
+    if (e && e[0] == '0') return nullptr;  // usable stays false
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return &ps;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return nullptr;
     ps.cus = prop.multiProcessorCount;
     ps.max_lds = (int)prop.maxSharedMemoryPerMultiProcessor;
-    if (hipHostMalloc((void**)&ps.error_host, 64, hipHostMallocMapped) != hipSuccess) return &ps;
+    if (hipHostMalloc((void**)&ps.error_host, 64, hipHostMallocMapped) != hipSuccess) return nullptr;
     *ps.error_host = 0u;
-    if (hipHostGetDevicePointer((void**)&ps.error_dev, ps.error_host, 0) != hipSuccess) return &ps;
-    if (hipMalloc((void**)&ps.mirror, 64) != hipSuccess || hipMemset(ps.mirror, 0, 64) != hipSuccess) return &ps;
+    if (hipHostGetDevicePointer((void**)&ps.error_dev, ps.error_host, 0) != hipSuccess) return nullptr;
+    if (hipMalloc((void**)&ps.mirror, 64) != hipSuccess || hipMemset(ps.mirror, 0, 64) != hipSuccess) return nullptr;
     // ~0.4 us per poll with s_sleep(4): 2^21 polls ~ 1 s before a workgroup gives up
     ps.spin_limit = 1u << 21;
-    if (hipFuncSetAttribute((const void*)m2d_gru_persist_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            140 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)m2d_gru_persist_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            140 * 1024) != hipSuccess)
-      return &ps;
-    if (hipFuncSetAttribute((const void*)m2d_gru_persist_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            140 * 1024) != hipSuccess)
-      return &ps;
+    for (const void* f : {(const void*)m2d_gru_persist_fwd_kernel<false>, (const void*)m2d_gru_persist_fwd_kernel<true>,
+                          (const void*)m2d_gru_persist_bwd_kernel})
+      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) != hipSuccess) return nullptr;
     ps.usable = true;
   }
   return ps.usable ? &ps : nullptr;
 }
+static GruPersistState* gru_persist_state_peek() { return gru_persist_state(false); }
 
-static size_t gru_persist_lds(int H) { (void)H; return (size_t)GRU_FWD_NW * 4 * 256 * sizeof(float); }  // the cross-wave sum only
-static size_t gru_persist_bwd_lds(int H) { (void)H; return (size_t)GRU_BWD_NW * 256 * sizeof(float); }  // the cross-wave sum only
+static const size_t GRU_PERSIST_FWD_LDS = (size_t)GRU_FWD_NW * 4 * 256 * sizeof(float);  // the cross-wave sum only
+static const size_t GRU_PERSIST_BWD_LDS = (size_t)GRU_BWD_NW * 256 * sizeof(float);      // the cross-wave sum only
 
-// every workgroup must be resident at once. ONE per CU: a workgroup is 8 waves of 131-174 VGPRs (the weight slices
+// THE decision for the persistent form: the state to launch with, or NULL (run the step launches). `elems`: elements
+// of the widest tensor the kernel addresses with 32-bit byte offsets.
+// Every workgroup must be resident at once. ONE per CU: a workgroup is 8 waves of 131-174 VGPRs (the weight slices
 // live in registers), i.e. two waves per SIMD, and a second workgroup's waves do not fit beside them - the LDS
 // footprint (32 KB / 8 KB) no longer says so by itself.
-static bool gru_persist_ok(dim3 grid, int H, int T, bool backward = false) {
-  if (H > 256 || T < 4) return false;
+static GruPersistState* gru_persist_plan(dim3 grid, int H, int T, long long elems, bool backward) {
+  if (H > 256 || T < 4) return nullptr;
   GruPersistState* ps = gru_persist_state();
-  if (!ps) return false;
-  const size_t lds = backward ? gru_persist_bwd_lds(H) : gru_persist_lds(H);
-  if ((int)lds > ps->max_lds) return false;
+  if (!ps || (int)(backward ? GRU_PERSIST_BWD_LDS : GRU_PERSIST_FWD_LDS) > ps->max_lds) return nullptr;
   const long long blocks = (long long)grid.x * grid.y * grid.z;
   // leave a margin: other streams' kernels (the noise GRU) need a place to run too
-  return blocks <= (long long)ps->cus * 3 / 4;
+  if (blocks > (long long)ps->cus * 3 / 4 || elems * 4 >= 0x7fffffffLL) return nullptr;
+  return ps;
+}
+
+// what both persistent argument structs take from the state
+template <class PersistArgs>
+static void gru_persist_fill(PersistArgs& pa, const GruPersistState* ps) {
+  pa.error = ps->error_dev; pa.mirror = ps->mirror; pa.spin_limit = ps->spin_limit;
 }
 
 extern "C" {
@@ -1076,41 +1072,33 @@ static int gru_stack_fwd(const char* name, const float* gi0, const float* const*
   a.B = B; a.T = T; a.H = H; a.L = L;
   dim3 grid(m2d_ceil_div(H, 16), m2d_ceil_div(B, 16), L);
   M2dProfScope prof(M2D_FAM_GRU, stream, 2.0 * B * 3.0 * H * H * (double)T * (2 * L - 1), 0.0, "gru_stack_fwd", B, T, H);
+  const auto persist_kernel = state ? m2d_gru_persist_fwd_kernel<true> : m2d_gru_persist_fwd_kernel<false>;
+  const auto step_kernel = state ? m2d_gru_stack_fwd_kernel<true> : m2d_gru_stack_fwd_kernel<false>;
   // `counters` non-NULL (the backward's scratch size; the forward only takes it as the request): run the recurrence
   // as ONE persistent launch when every workgroup fits on the chip at once
-  if (counters && gru_persist_ok(grid, H, T) && (long long)B * T * H * 4 < 0x7fffffffLL) {
-    GruPersistState* ps = gru_persist_state();
-    if (ps) {
-      // every output starts as the sentinel the consumers spin on (one memset when the layers' outputs are one
-      // allocation, as kernels.py makes them)
-      const size_t obytes = sizeof(float) * (size_t)B * T * H;
-      bool contiguous = true;
-      for (int l = 1; l < L; ++l) contiguous = contiguous && (out[l] == out[l - 1] + (size_t)B * T * H);
-      bool ok = true;
-      if (contiguous) ok = hipMemsetAsync(out[0], 0xFF, obytes * L, stream) == hipSuccess;
-      else
-        for (int l = 0; l < L; ++l) ok = ok && hipMemsetAsync(out[l], 0xFF, obytes, stream) == hipSuccess;
-      if (ok) {
-        GruPersistArgs pa;
-        pa.s = a;
-        pa.error = ps->error_dev;
-      pa.mirror = ps->mirror;
-        pa.spin_limit = ps->spin_limit;
-        if (state)
-          hipLaunchKernelGGL(m2d_gru_persist_fwd_kernel<true>, grid, dim3(64 * GRU_FWD_NW), gru_persist_lds(H), stream, pa);
-        else
-          hipLaunchKernelGGL(m2d_gru_persist_fwd_kernel<false>, grid, dim3(64 * GRU_FWD_NW), gru_persist_lds(H), stream, pa);
-        M2D_CHECK_LAUNCH("m2d_gru_persist_fwd_kernel");
-        return M2D_OK;
-      }
+  GruPersistState* ps;
+  if (counters && (ps = gru_persist_plan(grid, H, T, (long long)B * T * H, false))) {
+    // every output starts as the sentinel the consumers spin on (one memset when the layers' outputs are one
+    // allocation, as kernels.py makes them)
+    const size_t obytes = sizeof(float) * (size_t)B * T * H;
+    bool contiguous = true;
+    for (int l = 1; l < L; ++l) contiguous = contiguous && (out[l] == out[l - 1] + (size_t)B * T * H);
+    bool ok = true;
+    if (contiguous) ok = hipMemsetAsync(out[0], 0xFF, obytes * L, stream) == hipSuccess;
+    else
+      for (int l = 0; l < L; ++l) ok = ok && hipMemsetAsync(out[l], 0xFF, obytes, stream) == hipSuccess;
+    if (ok) {
+      GruPersistArgs pa;
+      pa.s = a;
+      gru_persist_fill(pa, ps);
+      hipLaunchKernelGGL(persist_kernel, grid, dim3(64 * GRU_FWD_NW), GRU_PERSIST_FWD_LDS, stream, pa);
+      M2D_CHECK_LAUNCH("m2d_gru_persist_fwd_kernel");
+      return M2D_OK;
     }
   }
   for (int d = 0; d < T + L - 1; ++d) {
     a.d = d;
-    if (state)
-      hipLaunchKernelGGL(m2d_gru_stack_fwd_kernel<true>, grid, dim3(64 * GRU_FWD_NW), 0, stream, a);
-    else
-      hipLaunchKernelGGL(m2d_gru_stack_fwd_kernel<false>, grid, dim3(64 * GRU_FWD_NW), 0, stream, a);
+    hipLaunchKernelGGL(step_kernel, grid, dim3(64 * GRU_FWD_NW), 0, stream, a);
   }
   M2D_CHECK_LAUNCH("m2d_gru_stack_fwd_kernel");
   return M2D_OK;
@@ -1216,16 +1204,14 @@ int m2d_gru_stack_bwd(const float* dout, const float* const* out, const float* c
   M2dProfScope prof(M2D_FAM_GRU, stream, 2.0 * B * 3.0 * H * H * (double)T * (2 * L - 1), 0.0, "gru_stack_bwd", B, T, H);
   // `counters` (optional, m2d_gru_stack_counters(B, L) unsigneds owned by this call): the whole BPTT as ONE
   // persistent launch when every workgroup fits on the chip at once
-  if (counters && gru_persist_ok(grid, H, T, true) && (long long)B * T * 3 * H * 4 < 0x7fffffffLL) {
-    GruPersistState* ps = gru_persist_state();
-    if (ps && hipMemsetAsync(counters, 0, sizeof(unsigned) * (size_t)m2d_gru_stack_counters(B, L), stream) == hipSuccess) {
+  GruPersistState* ps;
+  if (counters && (ps = gru_persist_plan(grid, H, T, (long long)B * T * 3 * H, true))) {
+    if (hipMemsetAsync(counters, 0, sizeof(unsigned) * (size_t)m2d_gru_stack_counters(B, L), stream) == hipSuccess) {
       GruPersistBwdArgs pa;
       pa.s = a;
       pa.counters = counters;
-      pa.error = ps->error_dev;
-      pa.mirror = ps->mirror;
-      pa.spin_limit = ps->spin_limit;
-      hipLaunchKernelGGL(m2d_gru_persist_bwd_kernel, grid, dim3(64 * GRU_BWD_NW), gru_persist_bwd_lds(H), stream, pa);
+      gru_persist_fill(pa, ps);
+      hipLaunchKernelGGL(m2d_gru_persist_bwd_kernel, grid, dim3(64 * GRU_BWD_NW), GRU_PERSIST_BWD_LDS, stream, pa);
       M2D_CHECK_LAUNCH("m2d_gru_persist_bwd_kernel");
       return M2D_OK;
     }

@@ -782,30 +782,6 @@ class HipKernels:
         return dx, dgamma, dbeta
 
     # ---------------------------------------------------------------- GRU
-    def gru_layer_fwd(self, gi, w_hh_t, b_hh, lengths=None, save=True):
-        """gi: (B, T, 3H) with b_ih added; w_hh_t: (H, 3H). Returns out (B,T,H), saved gates or None."""
-        dev = _chk(gi, w_hh_t, b_hh)
-        B, T, H3 = gi.shape
-        H = H3 // 3
-        out = torch.empty((B, T, H), dtype=torch.float32, device=dev)
-        saved = None
-        if save:
-            saved = torch.empty((4, B, T, H), dtype=torch.float32, device=dev)
-        _launch("m2d_gru_layer_fwd", dev, _ptr(gi), _ptr(w_hh_t), _ptr(b_hh), _ptr(lengths), _ptr(out),
-                _ptr(saved[0]) if save else 0, _ptr(saved[1]) if save else 0, _ptr(saved[2]) if save else 0,
-                _ptr(saved[3]) if save else 0, B, T, H)
-        return out, saved
-
-    def gru_layer_bwd(self, dout, out, saved, w_hh, lengths=None):
-        dev = _chk(dout, out, saved, w_hh)
-        B, T, H = out.shape
-        dgi = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
-        dgh = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
-        dh_buf = torch.empty((2, B, H), dtype=torch.float32, device=dev)
-        _launch("m2d_gru_layer_bwd", dev, _ptr(dout), _ptr(out), _ptr(saved[0]), _ptr(saved[1]), _ptr(saved[2]),
-                _ptr(saved[3]), _ptr(w_hh), _ptr(lengths), _ptr(dgi), _ptr(dgh), _ptr(dh_buf), B, T, H)
-        return dgi, dgh
-
     @staticmethod
     def _chk_lengths(lengths, dev, B):
         """per-sequence lengths handed to a kernel: a contiguous int32 tensor of B entries on the kernels' device"""
@@ -816,6 +792,29 @@ class HipKernels:
                                 % (dev, lengths.dtype, lengths.device))
         if lengths.numel() != B:
             raise _lib.M2dError("GRU lengths: %d entries for a batch of %d" % (lengths.numel(), B))
+
+    def gru_layer_fwd(self, gi, w_hh_t, b_hh, lengths=None, save=True):
+        """gi: (B, T, 3H) with b_ih added; w_hh_t: (H, 3H). Returns out (B,T,H), saved gates or None."""
+        dev = _chk(gi, w_hh_t, b_hh)
+        B, T, H3 = gi.shape
+        H = H3 // 3
+        self._chk_lengths(lengths, dev, B)
+        out = torch.empty((B, T, H), dtype=torch.float32, device=dev)
+        saved = torch.empty((4, B, T, H), dtype=torch.float32, device=dev) if save else None
+        _launch("m2d_gru_layer_fwd", dev, _ptr(gi), _ptr(w_hh_t), _ptr(b_hh), _ptr(lengths), _ptr(out),
+                *([_ptr(g) for g in saved] if save else [0] * 4), B, T, H)
+        return out, saved
+
+    def gru_layer_bwd(self, dout, out, saved, w_hh, lengths=None):
+        dev = _chk(dout, out, saved, w_hh)
+        B, T, H = out.shape
+        self._chk_lengths(lengths, dev, B)
+        dgi = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
+        dgh = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
+        dh_buf = torch.empty((2, B, H), dtype=torch.float32, device=dev)
+        _launch("m2d_gru_layer_bwd", dev, _ptr(dout), _ptr(out), *[_ptr(g) for g in saved], _ptr(w_hh), _ptr(lengths),
+                _ptr(dgi), _ptr(dgh), _ptr(dh_buf), B, T, H)
+        return dgi, dgh
 
     def gru_small_fwd(self, gi, w_hh, b_hh, lengths=None, save=True, with_out=True):
         """One GRU layer with 1 <= H <= 16 in one launch. gi: (B, T, 3H) with b_ih added; w_hh: (3H, H).
@@ -844,8 +843,16 @@ class HipKernels:
 
     @staticmethod
     def _ptr_array(tensors):
+        if tensors is None:
+            return None, None
         arr = (ctypes.c_void_p * len(tensors))(*[_ptr(t) for t in tensors])
         return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+    def _gru_counters(self, dev, B, L, persistent):
+        """the scratch that requests the persistent form (one launch for the whole recurrence; the library decides),
+        or None: step launches, by the caller's wish or after a recovered time-out (recover_async_fault)"""
+        return (torch.empty((_lib.lib().m2d_gru_stack_counters(B, L),), dtype=torch.int32, device=dev)
+                if (persistent and self.persistent_gru) else None)
 
     def gru_stack_fwd(self, gi0, w_ih_t, b_ih, w_hh_t, b_hh, lengths=None, save=True, persistent=True, h0=None,
                       want_state=False):
@@ -857,7 +864,7 @@ class HipKernels:
         dev = _chk(gi0, *[t for t in list(w_ih_t) + list(b_ih) + list(w_hh_t) + list(b_hh) if t is not None])
         B, T, H3 = gi0.shape
         H = H3 // 3
-        state = h0 is not None or want_state
+        self._chk_lengths(lengths, dev, B)
         if h0 is not None:
             h0 = list(h0)
             if len(h0) != L or any(tuple(t.shape) != (B, H) for t in h0) or _chk(*h0) != dev:
@@ -866,19 +873,12 @@ class HipKernels:
         outs = list(torch.empty((L, B, T, H), dtype=torch.float32, device=dev).unbind(0))
         saved = [torch.empty((4, B, T, H), dtype=torch.float32, device=dev) for _ in range(L)] if save else None
         h_n = torch.empty((L, B, H), dtype=torch.float32, device=dev) if want_state else None
-        keep = [self._ptr_array(v) for v in (w_ih_t, b_ih, w_hh_t, b_hh, outs)]
-        sv = self._ptr_array(saved) if save else (None, None)
-        hz = self._ptr_array(h0) if h0 is not None else (None, None)
-        hn = self._ptr_array(list(h_n.unbind(0))) if want_state else (None, None)
-        # scratch for the persistent form (one launch for the whole recurrence); the library decides
-        counters = (torch.empty((_lib.lib().m2d_gru_stack_counters(B, L),), dtype=torch.int32, device=dev)
-                    if (persistent and self.persistent_gru) else None)
-        if state:
-            _launch("m2d_gru_stack_fwd_state", dev, _ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1],
-                    keep[4][1], sv[1], _ptr(lengths), hz[1], hn[1], B, T, H, L, _ptr(counters))
-        else:
-            _launch("m2d_gru_stack_fwd", dev, _ptr(gi0), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
-                    sv[1], _ptr(lengths), B, T, H, L, _ptr(counters))
+        keep = [self._ptr_array(v) for v in (w_ih_t, b_ih, w_hh_t, b_hh, outs, saved, h0,
+                                             h_n.unbind(0) if want_state else None)]
+        counters = self._gru_counters(dev, B, L, persistent)
+        state = h0 is not None or want_state  # (without one, the entry point without: its name is in the error texts)
+        _launch("m2d_gru_stack_fwd_state" if state else "m2d_gru_stack_fwd", dev, _ptr(gi0), *[k[1] for k in keep[:6]],
+                _ptr(lengths), *([keep[6][1], keep[7][1]] if state else []), B, T, H, L, _ptr(counters))
         return (outs, saved, h_n) if want_state else (outs, saved)
 
     @staticmethod
@@ -930,14 +930,13 @@ class HipKernels:
         L = len(outs)
         dev = _chk(dout, *outs, *saved, *w_hh, *[t for t in w_ih if t is not None])
         B, T, H = outs[0].shape
+        self._chk_lengths(lengths, dev, B)
         dgi = [torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev) for _ in range(L)]
         dgh = [torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev) for _ in range(L)]
         dhb = [torch.empty((2, B, H), dtype=torch.float32, device=dev) for _ in range(L)]
         keep = [self._ptr_array(v) for v in (outs, saved, w_hh, w_ih, dgi, dgh, dhb)]
-        counters = (torch.empty((_lib.lib().m2d_gru_stack_counters(B, L),), dtype=torch.int32, device=dev)
-                    if (persistent and self.persistent_gru) else None)
-        _launch("m2d_gru_stack_bwd", dev, _ptr(dout), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1],
-                keep[5][1], keep[6][1], _ptr(lengths), B, T, H, L, _ptr(counters))
+        counters = self._gru_counters(dev, B, L, persistent)
+        _launch("m2d_gru_stack_bwd", dev, _ptr(dout), *[k[1] for k in keep], _ptr(lengths), B, T, H, L, _ptr(counters))
         return dgi, dgh
 
     # ---------------------------------------------------------------- gradient penalty

@@ -567,9 +567,20 @@ def batch_norm(x, gamma, beta, running_mean, running_var, training, eps=1e-5, mo
 
 
 # --------------------------------------------------------------------------------------- GRU
+def _gru_lengths(lengths, x, what):
+    """`lengths` (None, or any integer tensor or sequence, pack_padded_sequence's CPU int64 included) as the kernels take
+    it: a contiguous int32 tensor of B entries on x's device. One that is that already comes back as it is, no copy."""
+    if lengths is None:
+        return None
+    lengths = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).contiguous()
+    if lengths.numel() != x.shape[0]:
+        raise ValueError("%s: %d lengths for a batch of %d" % (what, lengths.numel(), x.shape[0]))
+    return lengths
+
+
 def _gru_layer_grads(x, w_ih, out, dgi, dgh, need_dx):
     """(dx or None, dW_ih, dW_hh, db_ih, db_hh) of one GRU layer from the pre-activation gradients dgi / dgh (B, T, 3H)
-    its BPTT kernel wrote: engine GEMMs over all T steps and channel sums."""
+    its BPTT kernel wrote: engine GEMMs over all T steps and channel sums. x: the layer's input (B, T, in)."""
     B, T, I = x.shape
     H = out.shape[2]
     k = K()
@@ -607,27 +618,34 @@ class _GRULayer(Function):
         return _gru_layer_grads(x, w_ih, out, dgi, dgh, ctx.needs_input_grad[0]) + (None, None)
 
 
+def _gru_stack_forward(x, params, lengths, save, hx=None, **state):
+    """What both forms of gru_stack run: contiguous parameters, layer 0's input projection over all T steps, the cached
+    weight transposes, one gru_stack_fwd (`state`: its keywords for a carried state) -> (x, [w_ih], [w_hh], its result)."""
+    L = len(params) // 4
+    w_ih, w_hh, b_ih, b_hh = ([_c(params[4 * l + i]) for l in range(L)] for i in range(4))
+    x = _c(x)
+    B, T, I = x.shape
+    H = w_hh[0].shape[1]
+    if hx is not None:
+        if tuple(hx.shape) != (L, B, H):
+            raise ValueError("gru_stack: hx of shape %s, (%d, %d, %d) expected" % (tuple(hx.shape), L, B, H))
+        state["h0"] = _c(hx)
+    k = K()
+    gi0 = k.gemm(0, x.view(B * T, I), w_ih[0], b_ih[0]).view(B, T, 3 * H)
+    return x, w_ih, w_hh, k.gru_stack_fwd(gi0, [None] + [k.transposed(w) for w in w_ih[1:]], [None] + b_ih[1:],
+                                          [k.transposed(w) for w in w_hh], b_hh, lengths, save, **state)
+
+
 class _GRUStack(Function):
     """All layers of an nn.GRU at once on the (layer, t) diagonal (T + L - 1 step launches)."""
 
     @staticmethod
     def forward(ctx, x, lengths, save, *params):
         ctx.set_materialize_grads(False)
-        L = len(params) // 4
-        w_ih = [_c(params[4 * l]) for l in range(L)]
-        w_hh = [_c(params[4 * l + 1]) for l in range(L)]
-        b_ih = [_c(params[4 * l + 2]) for l in range(L)]
-        b_hh = [_c(params[4 * l + 3]) for l in range(L)]
-        x = _c(x)
-        B, T, I = x.shape
-        H = w_hh[0].shape[1]
-        k = K()
-        gi0 = k.gemm(0, x.view(B * T, I), w_ih[0], b_ih[0]).view(B, T, 3 * H)
-        outs, saved = k.gru_stack_fwd(gi0, [None] + [k.transposed(w) for w in w_ih[1:]], [None] + b_ih[1:],
-                                      [k.transposed(w) for w in w_hh], b_hh, lengths, save)
+        x, w_ih, w_hh, (outs, saved) = _gru_stack_forward(x, params, lengths, save)
         if save:
             ctx.save_for_backward(x, lengths, *w_ih, *w_hh, *outs, *saved)
-            ctx.L = L
+            ctx.L = len(outs)
         return outs[-1]
 
     @staticmethod
@@ -640,20 +658,12 @@ class _GRUStack(Function):
         x, lengths = t[0], t[1]
         w_ih, w_hh = list(t[2:2 + L]), list(t[2 + L:2 + 2 * L])
         outs, saved = list(t[2 + 2 * L:2 + 3 * L]), list(t[2 + 3 * L:2 + 4 * L])
-        B, T, I = x.shape
-        H = w_hh[0].shape[1]
-        k = K()
-        dgi, dgh = k.gru_stack_bwd(_c(dout), outs, saved, w_hh, [None] + w_ih[1:], lengths,
-                                   persistent=os.environ.get("M2D_GRU_BWD_PERSIST", "1") != "0")
-        grads = []
-        for l in range(L):
-            dgi2, dgh2 = dgi[l].view(B * T, 3 * H), dgh[l].view(B * T, 3 * H)
-            inp = x.view(B * T, I) if l == 0 else outs[l - 1].view(B * T, H)
-            hprev = torch.cat((outs[l].new_zeros(B, 1, H), outs[l][:, :-1]), 1).contiguous().view(B * T, H)
-            grads += [k.gemm(2, dgi2, inp), k.gemm(2, dgh2, hprev), k.channel_sums(dgi2.view(B * T, 3 * H, 1)),
-                      k.channel_sums(dgh2.view(B * T, 3 * H, 1))]
-        dx = k.gemm(1, dgi[0].view(B * T, 3 * H), w_ih[0]).view(B, T, I) if ctx.needs_input_grad[0] else None
-        return (dx, None, None) + tuple(grads)
+        dgi, dgh = K().gru_stack_bwd(_c(dout), outs, saved, w_hh, [None] + w_ih[1:], lengths,
+                                     persistent=_gru_bwd_persist_enabled())
+        # layer by layer from the bottom, each as _gru_layer_grads orders it (dx comes first, for layer 0 alone)
+        grads = [_gru_layer_grads(x if l == 0 else outs[l - 1], w_ih[l], outs[l], dgi[l], dgh[l],
+                                  l == 0 and ctx.needs_input_grad[0]) for l in range(L)]
+        return (grads[0][0], None, None) + tuple(g for layer in grads for g in layer[1:])
 
 
 def gru_stack(x, params, lengths=None, hx=None, return_state=False):
@@ -661,6 +671,7 @@ def gru_stack(x, params, lengths=None, hx=None, return_state=False):
     hx: the initial state (L, B, H) (None: zeros); return_state: -> (out, h_n (L, B, H)), h_n being the state after
     step lengths[b] - 1 (T - 1 without lengths). With either, the call is inference only: there is no backward through
     a carried state, so a graph that would need one is refused."""
+    lengths = _gru_lengths(lengths, x, "gru_stack")
     if hx is None and not return_state:
         save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         return _GRUStack.apply(x, lengths, save, *params)
@@ -670,26 +681,13 @@ def gru_stack(x, params, lengths=None, hx=None, return_state=False):
                                "(detach it or run under torch.no_grad())")
         if x.requires_grad or any(p.requires_grad for p in params):
             raise RuntimeError("gru_stack: a carried state is inference only - run under torch.no_grad()")
-    L = len(params) // 4
-    w_ih = [_c(params[4 * l]) for l in range(L)]
-    w_hh = [_c(params[4 * l + 1]) for l in range(L)]
-    b_ih = [_c(params[4 * l + 2]) for l in range(L)]
-    b_hh = [_c(params[4 * l + 3]) for l in range(L)]
-    x = _c(x)
-    B, T, I = x.shape
-    H = w_hh[0].shape[1]
-    if hx is not None and tuple(hx.shape) != (L, B, H):
-        raise ValueError("gru_stack: hx of shape %s, (%d, %d, %d) expected" % (tuple(hx.shape), L, B, H))
-    k = K()
-    gi0 = k.gemm(0, x.view(B * T, I), w_ih[0], b_ih[0]).view(B, T, 3 * H)
-    outs, _, h_n = k.gru_stack_fwd(gi0, [None] + [k.transposed(w) for w in w_ih[1:]], [None] + b_ih[1:],
-                                   [k.transposed(w) for w in w_hh], b_hh, lengths, save=False,
-                                   h0=None if hx is None else _c(hx), want_state=True)
+    outs, _, h_n = _gru_stack_forward(x, params, lengths, False, hx, want_state=True)[3]
     return (outs[-1], h_n) if return_state else outs[-1]
 
 
 def gru_layer(x, w_ih, w_hh, b_ih, b_hh, lengths=None):
     """One nn.GRU layer (batch_first, h0 = 0) over a whole (B, T, in) sequence."""
+    lengths = _gru_lengths(lengths, x, "gru_layer")
     save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, w_ih, w_hh, b_ih, b_hh))
     return _GRULayer.apply(x, w_ih, w_hh, b_ih, b_hh, lengths, save)
 
@@ -700,6 +698,11 @@ GRU_SMALL_MAX = 16  # widest hidden size of m2d_gru_small_fwd / _bwd
 def _gru_small_enabled():
     """M2D_GRU_SMALL=0 sends every gru_final_state through gru_stack + a gather (A/B lever); read per call"""
     return os.environ.get("M2D_GRU_SMALL", "1") != "0"
+
+
+def _gru_bwd_persist_enabled():
+    """M2D_GRU_BWD_PERSIST=0: the stack's BPTT as step launches (tools/gru_bwd_probe.py flips it in-process); read per call"""
+    return os.environ.get("M2D_GRU_BWD_PERSIST", "1") != "0"
 
 
 class _GRUFinal(Function):
@@ -731,13 +734,9 @@ class _GRUFinal(Function):
 def gru_final_state(x, w_ih, w_hh, b_ih, b_hh, lengths=None):
     """h_n (B, H) of one nn.GRU layer (batch_first, h0 = 0) over (B, T, in): the state after step lengths[b] - 1
     (T - 1 without lengths). H <= 16 runs on the small-state kernels; wider states (or M2D_GRU_SMALL=0) run
-    gru_stack and gather the last valid step. `lengths`: any integer tensor or sequence of B entries (the CPU int64
-    lengths pack_padded_sequence takes included); it is moved to the device as int32."""
+    gru_stack and gather the last valid step. `lengths`: any integer tensor or sequence of B entries (_gru_lengths)."""
     H = w_hh.shape[1]
-    if lengths is not None:
-        lengths = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).contiguous()
-        if lengths.numel() != x.shape[0]:
-            raise ValueError("gru_final_state: %d lengths for a batch of %d" % (lengths.numel(), x.shape[0]))
+    lengths = _gru_lengths(lengths, x, "gru_final_state")
     if H <= GRU_SMALL_MAX and _gru_small_enabled():
         save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, w_ih, w_hh, b_ih, b_hh))
         return _GRUFinal.apply(x, w_ih, w_hh, b_ih, b_hh, lengths, save)

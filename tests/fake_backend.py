@@ -253,10 +253,13 @@ class FakeKernels:
         dx = gamma.view(shape) * save_invstd.view(shape) * (dz - (s1 / n).view(shape) - xh * (s2 / n).view(shape))
         return dx, s2, s1
 
-    def gru_layer_fwd(self, gi, w_hh_t, b_hh, lengths=None, save=True):
+    @staticmethod
+    def _gru_run(gi, w_hh_t, b_hh, lengths, save, h0=None):
+        """one layer's recurrence -> (out, saved or None, h_n): the state after step lengths[b] - 1 (T - 1 without)"""
         B, T, H3 = gi.shape
         H = H3 // 3
-        h = gi.new_zeros(B, H)
+        h = gi.new_zeros(B, H) if h0 is None else h0
+        h_n = h
         outs, rs, zs, ns, hns = [], [], [], [], []
         for t in range(T):
             gh = h @ w_hh_t + b_hh
@@ -266,11 +269,15 @@ class FakeKernels:
             h = (1 - z) * n + z * h
             if lengths is not None:
                 h = h * (t < lengths).to(h.dtype).view(B, 1)
+            h_n = h if lengths is None else torch.where((lengths == t + 1).view(B, 1), h, h_n)
             outs.append(h)
             rs.append(r), zs.append(z), ns.append(n), hns.append(gh[:, 2 * H:])
         out = torch.stack(outs, 1)
         saved = torch.stack([torch.stack(v, 1) for v in (rs, zs, ns, hns)], 0) if save else None
-        return out, saved
+        return out, saved, h_n
+
+    def gru_layer_fwd(self, gi, w_hh_t, b_hh, lengths=None, save=True):
+        return self._gru_run(gi, w_hh_t, b_hh, lengths, save)[:2]
 
     def gru_layer_bwd(self, dout, out, saved, w_hh, lengths=None):
         B, T, H = out.shape
@@ -294,13 +301,28 @@ class FakeKernels:
             dh_next = dh
         return dgi, dgh
 
-    def gru_stack_fwd(self, gi0, w_ih_t, b_ih, w_hh_t, b_hh, lengths=None, save=True):
-        outs, saved = [], []
+    def gru_small_fwd(self, gi, w_hh, b_hh, lengths=None, save=True, with_out=True):
+        out, saved, h_n = self._gru_run(gi, w_hh.t(), b_hh, lengths, save)
+        return (out if (with_out or save) else None), h_n, saved
+
+    def gru_small_bwd(self, dout, dh_n, out, saved, w_hh, lengths=None):
+        """dh_n reaches the recurrence at step lengths[b] - 1 (T - 1 without lengths): h_n is that step's output"""
+        B, T, H = out.shape
+        d = torch.zeros_like(out) if dout is None else dout.clone()
+        if dh_n is not None:
+            last = torch.full((B,), T - 1, dtype=torch.long) if lengths is None else lengths.long() - 1
+            d[torch.arange(B), last] += dh_n
+        return self.gru_layer_bwd(d, out, saved, w_hh, lengths)
+
+    def gru_stack_fwd(self, gi0, w_ih_t, b_ih, w_hh_t, b_hh, lengths=None, save=True, persistent=True, h0=None,
+                      want_state=False):
+        outs, saved, h_n = [], [], []
         for l in range(len(w_hh_t)):
             gi = gi0 if l == 0 else outs[-1] @ w_ih_t[l] + b_ih[l]
-            o, s = self.gru_layer_fwd(gi, w_hh_t[l], b_hh[l], lengths, save)
-            outs.append(o), saved.append(s)
-        return outs, (saved if save else None)
+            o, s, h = self._gru_run(gi, w_hh_t[l], b_hh[l], lengths, save, None if h0 is None else h0[l])
+            outs.append(o), saved.append(s), h_n.append(h)
+        saved = saved if save else None
+        return (outs, saved, torch.stack(h_n, 0)) if want_state else (outs, saved)
 
     def gru_stack_bwd(self, dout, outs, saved, w_hh, w_ih, lengths=None, persistent=True):
         L = len(outs)

@@ -593,6 +593,42 @@ def test_gru_stack_lengths():
     assert rel_err(out, ref) < 1e-5
 
 
+def _gru_wrapper_calls():
+    """name -> call(lengths) of each GRU wrapper of the kernel layer with otherwise valid arguments"""
+    B, T, H, L = 3, 5, 18, 2
+    k = K()
+    z = lambda *shape: torch.zeros(*shape, device=DEV)
+    gi, out, saved, dout = z(B, T, 3 * H), z(B, T, H), z(4, B, T, H), z(B, T, H)
+    w, wt, b = z(3 * H, H), z(H, 3 * H), z(3 * H)
+    return B, {
+        "gru_layer_fwd": lambda n: k.gru_layer_fwd(gi, wt, b, n),
+        "gru_layer_bwd": lambda n: k.gru_layer_bwd(dout, out, saved, w, n),
+        "gru_small_fwd": lambda n: k.gru_small_fwd(gi, w, b, n),
+        "gru_small_bwd": lambda n: k.gru_small_bwd(dout, None, out, saved, w, n),
+        "gru_stack_fwd": lambda n: k.gru_stack_fwd(gi, [None] + [wt] * (L - 1), [None] + [b] * (L - 1), [wt] * L, [b] * L, n),
+        "gru_stack_bwd": lambda n: k.gru_stack_bwd(dout, [out] * L, [saved] * L, [w] * L, [None] + [w] * (L - 1), n),
+    }
+
+
+@pytest.mark.parametrize("name", ["gru_layer_fwd", "gru_layer_bwd", "gru_small_fwd", "gru_small_bwd", "gru_stack_fwd",
+                                  "gru_stack_bwd"])
+def test_gru_wrappers_refuse_lengths_a_kernel_would_misread_before_any_launch(name):
+    """int64 entries (a kernel would read them as pairs of int32) and a wrong count: refused by the wrapper's own check
+    (its text, not the library's), with no launch of the GRU family"""
+    from music2dance_amd._lib import M2dError
+    B, calls = _gru_wrapper_calls()
+    k = K()
+    k.prof_begin()
+    try:
+        with pytest.raises(M2dError, match="GRU lengths must be a contiguous int32 tensor"):
+            calls[name](torch.ones(B, dtype=torch.int64, device=DEV))
+        with pytest.raises(M2dError, match="GRU lengths: %d entries for a batch of %d" % (B + 1, B)):
+            calls[name](torch.ones(B + 1, dtype=torch.int32, device=DEV))
+    finally:
+        stats = k.prof_end()
+    assert stats["gru"]["launches"] == 0
+
+
 def test_conv1d_random_shapes():
     """Seeded sweep over conv geometries (tails of every kind, padding wider than the kernel
     reach, strides that do not divide, batches that split tiles across samples), plain and
