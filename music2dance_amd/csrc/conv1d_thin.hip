@@ -838,17 +838,28 @@ bool m2d_thin_long_applicable(int Cin, int Cout, int ks, int stride, int pad, in
 #define THIN_LONG_MAX_WAVES (512 * 8)
 size_t m2d_thin_long_stats_ws(int B, int Lout) { (void)B; (void)Lout; return (size_t)THIN_LONG_MAX_WAVES * 64 * sizeof(float) + (size_t)256 * 32 * 2 * sizeof(double); }
 
+// LDS of a workgroup of thin_long_fwd_kernel<KS, S>: the weight image + 8 waves' segment and accumulator images
+template <int KS, int S>
+static constexpr size_t thin_long_lds() {
+  constexpr int SEG4 = (31 * S + KS + 3 + 3) / 4;
+  return (size_t)(KS * 32 + 8 * (SEG4 * 4 + 32 * 36)) * sizeof(float);
+}
+static int thin_long_tiles_per_row(int Lout) { return Lout / 32; }   // (m2d_thin_long_applicable: whole tiles)
+// workgroups of the persistent long forward: one workgroup (8 waves) per CU, two when the LDS image is small enough for
+// two to be resident; fewer when there are not that many groups of eight tiles
+static int thin_long_grid(size_t lds, int total_tiles) {
+  const int per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
+  const int need = m2d_ceil_div(total_tiles, 8);
+  return need < 256 * per_cu ? need : 256 * per_cu;
+}
+
 template <int KS, int S>
 static int thin_long_launch(const ThinArgs& a, int tpr, int total, hipStream_t stream, int* waves) {
-  constexpr int SEG4 = (31 * S + KS + 3 + 3) / 4;
-  constexpr size_t lds = (size_t)(KS * 32 + 8 * (SEG4 * 4 + 32 * 36)) * sizeof(float);
+  constexpr size_t lds = thin_long_lds<KS, S>();
   static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_long_fwd_kernel<KS, S>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
   if (!attr_ok) M2D_FAIL(M2D_ERR_HIP, "m2d_conv1d_fwd (long single-channel kernel): cannot reserve %zu bytes of LDS", lds);
-  // one workgroup (8 waves) per CU, two when the LDS image is small enough for two to be resident
-  const int per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
-  const int need = m2d_ceil_div(total, 8);
-  const int grid = need < 256 * per_cu ? need : 256 * per_cu;
+  const int grid = thin_long_grid(lds, total);
   *waves = grid * 8;
   hipLaunchKernelGGL((thin_long_fwd_kernel<KS, S>), dim3(grid), dim3(512), lds, stream, a, tpr, total);
   M2D_CHECK_LAUNCH("thin_long_fwd_kernel");
@@ -861,7 +872,7 @@ int m2d_thin_long_fwd(const float* x, const float* w, const float* bias, float* 
   ThinArgs a;
   memset(&a, 0, sizeof(a));
   if (wv) { a.xT = wv->T; a.xS = wv->S; a.xhop = wv->hop; }
-  const int tpr = Lout / 32;
+  const int tpr = thin_long_tiles_per_row(Lout);
   if ((long long)B * tpr >= (1LL << 30) || (long long)Lout * 32 * 4 >= (1LL << 31) || (long long)L * 4 >= (1LL << 31))
     M2D_FAIL(M2D_ERR_RANGE, "m2d_conv1d_fwd (long single-channel kernel): too many tiles / a sample beyond 2 GiB");
   const int total = B * tpr;
@@ -882,6 +893,9 @@ int m2d_thin_long_fwd(const float* x, const float* w, const float* bias, float* 
   return M2D_OK;
 }
 
+// backward-data: the positions q a sample's blocks share out (the kernel's nq: dx[S q + rho - pad], q in [0, nq))
+static int thin_bwd_data_nq(int L, int stride, int pad) { return (L - 1 + pad) / stride + 1; }
+
 int m2d_thin_bwd_data(const float* dy, const float* w, float* dx, int B, int L, int Cout, int ks, int stride,
                       int pad, int Lout, const float* dy_mask, float dy_mask_slope, hipStream_t stream) {
   ThinArgs a;
@@ -889,7 +903,7 @@ int m2d_thin_bwd_data(const float* dy, const float* w, float* dx, int B, int L, 
   a.dy = dy; a.w = w; a.mask = dy_mask; a.out = dx;
   a.B = B; a.L = L; a.Cout = Cout; a.ks = ks; a.stride = stride; a.pad = pad; a.Lout = Lout;
   a.mask_slope = dy_mask_slope;
-  const int nq = (L - 1 + pad) / stride + 1;
+  const int nq = thin_bwd_data_nq(L, stride, pad);
   M2dProfScope prof(M2D_FAM_POINTWISE, stream, 2.0 * B * Lout * (double)Cout * ks,
                     4.0 * B * ((double)L + (double)Cout * Lout * (dy_mask ? 2 : 1)), "thin_conv_bwd_data", 1, B * L, Cout * ks);
   a.chunk = thin_bw_chunk(B, nq);
@@ -926,4 +940,37 @@ int m2d_thin_bwd_weight(const float* x, const float* dy, float* dw, float* dbias
                      dim3(256), 0, stream, (const float*)ws, dw, nchunk * B, Cout * ks, (const float*)a.out2, dbias, Cout);
   M2D_CHECK_LAUNCH("thin_bwd_weight_mfma_kernel");
   return M2D_OK;
+}
+
+// test-only (tests/thin_cases.py binds it with ctypes; not part of include/m2d.h): how the launchers above would share
+// out a Cin = 1, Cout = 32 conv - from the very functions they call, so that the tests know which shapes make a wave
+// walk several tiles. Touches no stream and no device.
+//   which 0 k25 forward, 1 long forward:        out = {total tiles, waves of the grid, 0}
+//   which 2 backward-weight, 3 backward-data:   out = {positions per sample (Lout / nq), chunk, blocks per sample}
+// A conv the pass has no kernel for: out = {-1, -1, -1}.
+extern "C" void m2d_debug_thin_schedule(int which, int B, int L, int ks, int stride, int pad, int* out) {
+  out[0] = out[1] = out[2] = -1;
+  if (B <= 0 || L <= 0 || ks <= 0 || stride <= 0 || pad < 0 || L + 2 * pad < ks) return;
+  const int Lout = (L + 2 * pad - ks) / stride + 1;
+  if (which == 1) {
+    const int kind = thin_long_kind(1, 32, ks, stride);
+    if (!kind || !m2d_thin_long_applicable(1, 32, ks, stride, pad, L)) return;
+    const int total = B * thin_long_tiles_per_row(Lout);
+    out[0] = total;
+    out[1] = thin_long_grid(kind == 1 ? thin_long_lds<250, 50>() : thin_long_lds<160, 4>(), total) * 8;
+    out[2] = 0;
+    return;
+  }
+  if (!thin_ok(1, 32, ks, stride)) return;
+  if (which == 0) {
+    const int total = B * thin_fwd_tiles_per_row(Lout);
+    out[0] = total;
+    out[1] = thin_fwd_grid(total) * 4;
+    out[2] = 0;
+  } else if (which == 2 || which == 3) {
+    const int n = which == 2 ? Lout : thin_bwd_data_nq(L, stride, pad);
+    out[0] = n;
+    out[1] = thin_bw_chunk(B, n);
+    out[2] = m2d_ceil_div(n, out[1]);
+  }
 }

@@ -1,7 +1,8 @@
 """Dataset side of the train scripts: music2dance_amd.data / losses.jerkiness against
 OUTPUTS of the reference's own code (tests/golden/data.npz, written by make_golden.py::case_data from
 utils.py:15-201,245-248,320-326, losses.py:85-89 and the split block of phase3/train.py:112-143).
-Host logic runs here; the two HIP kernels behind it (m2d_jerk_mean_fwd, m2d_affine_cols) are checked on the GPU box."""
+Host logic runs here; the two HIP kernels behind it (m2d_jerk_mean_fwd, m2d_affine_cols) are checked
+by tests/test_gpu_pointwise_gaps.py."""
 import os
 
 import numpy as np
