@@ -289,8 +289,8 @@ class FakeKernels:
             dh = dout[:, t].clone()
             if dh_next is not None:
                 dh = dh + dh_next * z_s[:, t + 1] + dgh[:, t + 1] @ w_hh
-            if lengths is not None:
-                dh = dh * (t < lengths).to(dh.dtype).view(B, 1)
+            if lengths is not None:  # a select, as in the kernels: whatever dout holds past a length is never used
+                dh = torch.where((t < lengths).view(B, 1), dh, torch.zeros_like(dh))
             r, z, n, hn = r_s[:, t], z_s[:, t], n_s[:, t], hn_s[:, t]
             hprev = out[:, t - 1] if t > 0 else torch.zeros_like(n)
             dn = dh * (1 - z) * (1 - n * n)
