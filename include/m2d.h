@@ -433,6 +433,23 @@ int m2d_randn_frames(float* out, unsigned long long seed, long long frame0, int 
  * a disk covers (c - px)^2 + (r - py)^2 <= 16, a segment the pixels at squared distance <= 1.
  * height, width in [1, 4096]; n_frames 0: nothing to do. Deterministic, no atomics. */
 int m2d_render_sticks(const float* poses, long n_frames, int height, int width, unsigned char* out, void* stream);
+/* Baseline JPEG streams of frames (n_frames, height, width, 3) uint8 RGB on the device (contiguous, any byte
+ * alignment), one complete stream per frame: JFIF, 8 bits, 4:4:4, one interleaved scan, the standard's typical Huffman
+ * tables, a restart interval of one row of 8 x 8 blocks; integer colour transform, DCT and quantisation, stated in
+ * numpy by tests/jpeg_rule.py, which the bytes equal. qtabs: HOST memory, 128 bytes, the
+ * luminance then the chrominance quantisation table in row-major order, entries 1..255 (read before the call returns).
+ * out: device buffer of `capacity` bytes that receives the streams back to back; offsets: n_frames + 1 int64 on the
+ * device, frame i occupies out[offsets[i], offsets[i + 1]). offsets are always written. If offsets[n_frames] > capacity
+ * nothing is written to out (no truncation): call again with that capacity. Never writes out of [0, offsets[n_frames])
+ * nor past capacity. workspace: m2d_jpeg_workspace_bytes(n_frames, height, width) bytes, 16-byte aligned (int16
+ * coefficients of every block, row and frame sizes). Five launches on `stream`; deterministic, no host
+ * synchronisation, no allocation, capturable. height, width in [1, 4096]; n_frames 0: nothing to do.
+ * M2D_ERR_ARG: sizes out of range, a null pointer, a zero table entry; M2D_ERR_WORKSPACE; M2D_ERR_RANGE: more rows of
+ * blocks than one launch takes. */
+size_t m2d_jpeg_workspace_bytes(long n_frames, int height, int width);
+int m2d_jpeg_encode(const unsigned char* frames, long n_frames, int height, int width, const unsigned char* qtabs,
+                    unsigned char* out, long long capacity, long long* offsets, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 /* ---- polyphase FIR resampling of audio rows (change_rate.py:6-8: the reference shells out to sox) -----------------
  * Row b of x (B rows, ldx floats apart) holds the samples with ABSOLUTE indices [x0, x0 + nx); every other sample is

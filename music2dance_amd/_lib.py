@@ -118,6 +118,8 @@ SIGNATURES = {
     "m2d_dropout": (_I, [_F, _F, _F, _c.c_longlong, _f, _f, _c.c_ulonglong, _c.c_ulonglong, _I, _F]),
     "m2d_randn_frames": (_I, [_F, _c.c_ulonglong, _c.c_longlong, _I, _I, _I, _F]),
     "m2d_render_sticks": (_I, [_F, _L, _I, _I, _F, _F]),
+    "m2d_jpeg_workspace_bytes": (_S, [_L, _I, _I]),
+    "m2d_jpeg_encode": (_I, [_F, _L, _I, _I, _c.c_char_p, _F, _c.c_longlong, _F, _F, _S, _F]),
     "m2d_resample_poly": (_I, [_F, _c.c_longlong, _I, _c.c_longlong, _F, _I, _I, _I, _F, _c.c_longlong, _I, _c.c_longlong,
                                 _I, _F]),
     "m2d_stft_image_elems": (_S, [_I]),

@@ -1092,6 +1092,35 @@ class HipKernels:
         _launch("m2d_render_sticks", dev, _ptr(poses), n, int(height), int(width), _ptr(o))
         return o
 
+    def jpeg_encode(self, frames, qtabs, capacity=None):
+        """frames (n, H, W, 3) uint8 RGB on a HIP device (contiguous, any byte alignment), qtabs two quantisation
+        tables of 64 entries in 1..255 (row-major) -> (out, offsets): the frames' JPEG streams back to back in the
+        uint8 device buffer `out` of `capacity` bytes (default: the raw frame bytes) and the int64 device tensor
+        offsets (n + 1). When offsets[n] exceeds the capacity nothing was written: call again with that capacity
+        (m2d_jpeg_encode; no host synchronisation here)"""
+        if not torch.is_tensor(frames) or not frames.is_cuda:
+            raise _lib.M2dError("jpeg_encode: frames must be a tensor on a HIP device; there is no CPU path")
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise _lib.M2dError("jpeg_encode: frames must be uint8 (n, H, W, 3), got %s %s"
+                                % (frames.dtype, tuple(frames.shape)))
+        if not frames.is_contiguous():
+            raise _lib.M2dError("jpeg_encode: frames must be contiguous")
+        n, H, W = (int(s) for s in frames.shape[:3])
+        if not (1 <= H <= 4096 and 1 <= W <= 4096):
+            raise _lib.M2dError("jpeg_encode: height and width must lie in [1, 4096], got %d x %d" % (H, W))
+        q = [int(v) for t in qtabs for v in t]
+        if len(q) != 128 or not all(1 <= v <= 255 for v in q):
+            raise _lib.M2dError("jpeg_encode: qtabs must be two tables of 64 entries in 1..255")
+        dev = frames.device
+        cap = n * H * W * 3 if capacity is None else int(capacity)
+        if cap < 0:
+            raise _lib.M2dError("jpeg_encode: capacity < 0")
+        out = torch.empty((cap,), dtype=torch.uint8, device=dev)
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        ws, nws = _workspace(dev, "m2d_jpeg_workspace_bytes", n, H, W)
+        _launch("m2d_jpeg_encode", dev, _ptr(frames), n, H, W, bytes(q), _ptr(out), cap, _ptr(offsets), _ptr(ws), nws)
+        return out, offsets
+
     @staticmethod
     def _chk_audio_rows(t, what):
         """fp32 rows on a HIP device, unit stride inside a row (a column slice of a wider buffer is fine) -> leading

@@ -2,7 +2,7 @@
 
     python -m music2dance_amd.phase3.generate -c music2dance_amd/phase3/configs/default.yaml -l <logdir> \
         [--gen-weights PATH] (--audio a.wav [b.wav ...] | --val | --synthetic) [--chunk-frames N] [--seed S] \
-        [--folder DIR] [-d N] [--video] [--resampler {fft,poly}] [--beat-align]
+        [--folder DIR] [-d N] [--video [--encoder {pil,hip}]] [--resampler {fft,poly}] [--beat-align]
 
 The reference generates a 30-second sample in phase3/test.py:64-72 (with a broken call) and says its generator
 handles tracks of any length. Frame t of a track reads the audio window track[t hop - left, t hop - left + window)
@@ -18,7 +18,9 @@ visualize.frame_to_vid takes), and <logdir>/samples/generation.json (strict JSON
 seconds of audio, the chunk size, the wall time, the GPU time per chunk (p50 / p99) and the real-time factor
 (seconds of audio per second of wall time). With --video each saved array is also rendered to
 <logdir>/samples/<name>.avi (visualize.frame_to_vid at the config's video_rate), and its track entry gains `video`,
-`render_ms` (device time of the render launches) and `video_s` (wall time of the whole write).
+`render_ms` (device time of the render launches) and `video_s` (wall time of the whole write). --encoder chooses the
+JPEG encoder of that video (pil: on the host, the default; hip: m2d_jpeg_encode on the device); when it is given the
+track entry also records `encoder`.
 
 --resampler: how an --audio file that is not at the config's audio_rate gets there. `fft` (the default) converts the
 whole file on the host with scipy.signal.resample before anything is generated, as SequenceDataset.resample_audio does.
@@ -173,6 +175,8 @@ def parse_args(argv=None):
     ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
     ap.add_argument("--video", action="store_true", help="also render each saved dance to <logdir>/samples/<name>.avi "
                                                          "(300 x 300 stick figures at the config's video_rate)")
+    ap.add_argument("--encoder", choices=("pil", "hip"), default=None,
+                    help="with --video: the JPEG encoder, pil = on the host (the default), hip = on the device")
     ap.add_argument("--resampler", choices=("fft", "poly"), default="fft",
                     help="rate conversion of --audio files: fft = scipy.signal.resample of the whole file on the host, "
                          "poly = the polyphase filter on the device, streamed with the chunks")
@@ -353,8 +357,13 @@ def generate(opts, cfg, device):
         if getattr(opts, "video", False):
             from .. import visualize
             path = os.path.join(outdir, name + ".avi")
-            vid = visualize.frame_to_vid(saved, path, ds["video_rate"])
+            encoder = getattr(opts, "encoder", None)
+            # the keyword only when it is not the default: frame_to_vid is the reference's three-argument call
+            kw = {} if encoder in (None, "pil") else {"encoder": encoder}
+            vid = visualize.frame_to_vid(saved, path, ds["video_rate"], **kw)
             res["tracks"][-1].update(video=path, render_ms=vid["render_ms"], video_s=vid["wall_s"])
+            if encoder is not None:
+                res["tracks"][-1].update(encoder=encoder)
     with open(os.path.join(outdir, "generation.json"), "w") as f:
         json.dump(json_safe(res), f, indent=1, allow_nan=False)
     return res

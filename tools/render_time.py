@@ -2,9 +2,12 @@
 In one process it times, with HIP events after warm-up,
   * m2d_render_sticks over the whole track in one launch (--reps launches, median and best);
   * a plain device fill (torch fill_) of the same output buffer, the bound the render launch is measured against;
-  * visualize.frame_to_vid end to end, split into render, device-to-host copy, JPEG encode and mux.
+  * visualize.frame_to_vid end to end, split into render, device-to-host copy, JPEG encode and mux: --pairs times
+    with encoder="pil" and encoder="hip" in turn, so that both see the same clocks and neighbours;
+  * m2d_jpeg_encode on one chunk of CHUNK_FRAMES rendered frames: device time per chunk, and the bytes the launches
+    move (frames read once, int16 coefficients written once and read three times, streams written) per second.
 
-    python tools/render_time.py [--frames 4500] [--reps 30] [--poses POSES.npy] [--json PATH]
+    python tools/render_time.py [--frames 4500] [--reps 30] [--pairs 3] [--poses POSES.npy] [--json PATH]
 
 Without --poses the dance is synthetic: a figure with joints spread over about 180 x 240 pixels that sways and turns
 frame by frame; its segments cross more of the canvas than a generated dance's do, so fewer tiles take the
@@ -58,6 +61,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4500)
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--pairs", type=int, default=3, help="frame_to_vid runs per encoder, alternated")
     ap.add_argument("--poses", type=str, default=None, help="a (T, 23, 3) .npy instead of the synthetic dance")
     ap.add_argument("--json", type=str, default=None)
     opts = ap.parse_args()
@@ -87,12 +91,33 @@ def main():
     res["figure_pixel_share"] = round(figure, 4)
     del out
     torch.cuda.empty_cache()
+    # the encode launches on one chunk of the product path
+    k_frames = min(n, visualize.CHUNK_FRAMES)
+    chunk = k.render_sticks(x[:k_frames], 300, 300)
+    qtabs = visualize.jpeg_tables(95)[:2]
+    enc = event_times(lambda: k.jpeg_encode(chunk, qtabs), opts.reps)
+    k.check_async_errors()
+    _, offsets = k.jpeg_encode(chunk, qtabs)
+    stream_bytes = int(offsets[-1])
+    coef_bytes = k_frames * 38 * 38 * 384
+    moved = chunk.numel() + 4 * coef_bytes + stream_bytes   # coefficients: written once, walked three times
+    med = statistics.median(enc)
+    res["encode_chunk"] = {"frames": k_frames, "ms_median": round(med, 4), "ms_best": round(min(enc), 4),
+                           "stream_bytes": stream_bytes, "moved_bytes": moved,
+                           "moved_TBps_median": round(moved / med / 1e9, 3)}
+    del chunk
+    torch.cuda.empty_cache()
+    runs = []
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "dance.avi")
-        visualize.frame_to_vid(poses[:min(n, 64)], path, 25)   # warm-up: code objects, PIL
-        split = visualize.frame_to_vid(poses, path, 25)
-        split["file_bytes"] = os.path.getsize(path)
-    res["frame_to_vid"] = {key: round(v, 4) if isinstance(v, float) else v for key, v in split.items()}
+        for encoder in visualize.ENCODERS:   # warm-up: code objects, PIL
+            visualize.frame_to_vid(poses[:min(n, 64)], path, 25, encoder=encoder)
+        for _ in range(opts.pairs):
+            for encoder in visualize.ENCODERS:
+                split = visualize.frame_to_vid(poses, path, 25, encoder=encoder)
+                split["file_bytes"] = os.path.getsize(path)
+                runs.append({key: round(v, 4) if isinstance(v, float) else v for key, v in split.items()})
+    res["frame_to_vid"] = runs
     print(json.dumps(res))
     if opts.json:
         os.makedirs(os.path.dirname(os.path.abspath(opts.json)), exist_ok=True)
