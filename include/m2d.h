@@ -558,6 +558,32 @@ size_t m2d_pairwise_mean_dist_workspace_bytes(int G, int K);
 int m2d_pairwise_mean_dist(const float* X, long long ldx, int G, int K, int D, double* out, void* ws, size_t ws_bytes,
                            void* stream);
 
+/* ---- nearest-neighbour queries between two sets of rows (metrics.py; no counterpart in the
+ * reference) -------------------------------------------------------------------------------------------------------
+ * Rows are fp32 vectors of dimension D in [1, 128], ld* floats apart (a column block of a wider buffer is taken in
+ * place). d2(x, y) = sum_d (x_d - y_d)^2: the difference in fp32, one fmaf chain over d ascending from 0, never the Gram
+ * identity. d2(x, y) and d2(y, x) are the same bits; a row's results depend on no other query row of the call, nor on how
+ * the library tiles or splits the work; no atomics: results are bit-identical from run to run. All comparisons are on
+ * squared distances. Non-finite inputs neither hang nor fault; what they give is unspecified. A null or a host pointer
+ * is refused (M2D_ERR_ARG, nothing launched).
+ *
+ * m2d_knn_radii: r2[i] = the k-th smallest of d2(X_i, X_j) over j != i - the row itself is excluded by INDEX, duplicates
+ * of it count, with their multiplicity. M2D_ERR_ARG: k outside [1, m2d_knn_max_k()] (10), N <= k, D outside [1, 128],
+ * ldx < D; M2D_ERR_WORKSPACE: ws too small.
+ *
+ * m2d_ball_query, per query row j of Q (M rows) against P (N rows):
+ *   count[j]  = #{i : d2(Q_j, P_i) <= r2[i]}  (inclusive; r2 (N) and count (M) are given together or both NULL),
+ *   nn_d2[j]  = min_i d2(Q_j, P_i),  nn_idx[j] = the smallest i that attains it.
+ * M2D_ERR_ARG: M or N <= 0, D outside [1, 128], a stride below D, only one of r2 / count; M2D_ERR_WORKSPACE.
+ * Both: two launches on `stream` (the tiles, each workgroup over its share of the reference rows, into the workspace;
+ * then the merge in ascending order of the shares), no host synchronisation. */
+int m2d_knn_max_k(void);
+size_t m2d_knn_radii_workspace_bytes(int N, int k);
+int m2d_knn_radii(const float* X, long long ldx, int N, int D, int k, float* r2, void* ws, size_t ws_bytes, void* stream);
+size_t m2d_ball_query_workspace_bytes(int M, int N);
+int m2d_ball_query(const float* Q, long long ldq, int M, const float* P, long long ldp, int N, int D, const float* r2,
+                   int* count, float* nn_d2, int* nn_idx, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

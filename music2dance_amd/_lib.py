@@ -139,6 +139,11 @@ SIGNATURES = {
     "m2d_frechet": (_I, [_F, _F, _F, _F, _I, _I, _F, _F, _S, _F]),
     "m2d_pairwise_mean_dist_workspace_bytes": (_S, [_I, _I]),
     "m2d_pairwise_mean_dist": (_I, [_F, _c.c_longlong, _I, _I, _I, _F, _F, _S, _F]),
+    "m2d_knn_max_k": (_I, []),
+    "m2d_knn_radii_workspace_bytes": (_S, [_I, _I]),
+    "m2d_knn_radii": (_I, [_F, _c.c_longlong, _I, _I, _I, _F, _F, _S, _F]),
+    "m2d_ball_query_workspace_bytes": (_S, [_I, _I]),
+    "m2d_ball_query": (_I, [_F, _c.c_longlong, _I, _F, _c.c_longlong, _I, _I, _F, _F, _F, _F, _F, _S, _F]),
 }
 
 _lib = None

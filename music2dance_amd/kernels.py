@@ -1329,6 +1329,40 @@ class HipKernels:
         _launch("m2d_pairwise_mean_dist", dev, _ptr(X), ldx, G, K, D, _ptr(out), _ptr(ws), nws)
         return out
 
+    # ---------------------------------------------------------------- nearest-neighbour queries (metrics.py)
+    def knn_max_k(self):
+        return _lib.lib().m2d_knn_max_k()
+
+    def knn_radii(self, X, k):
+        """X (N, D) fp32, N >= k + 1, 1 <= k <= knn_max_k() -> r2 (N,) fp32: the k-th smallest squared distance of
+        each row to the other rows, the row itself excluded by index (m2d_knn_radii)"""
+        dev, ldx = self._rows2d("knn_radii", X)
+        N, D = X.shape
+        r2 = torch.empty((N,), dtype=torch.float32, device=dev)
+        ws, nws = _workspace(dev, "m2d_knn_radii_workspace_bytes", N, int(k))
+        _launch("m2d_knn_radii", dev, _ptr(X), ldx, N, D, int(k), _ptr(r2), _ptr(ws), nws)
+        return r2
+
+    def ball_query(self, Q, P, r2=None):
+        """Q (M, D), P (N, D) fp32, r2 (N,) fp32 or None -> (count (M,) int32 = #{i : d2(Q_j, P_i) <= r2[i]} or None,
+        nn_d2 (M,) fp32 = min_i d2(Q_j, P_i), nn_idx (M,) int32 = the smallest index attaining it) (m2d_ball_query)"""
+        dev, ldq = self._rows2d("ball_query", Q)
+        devp, ldp = self._rows2d("ball_query", P)
+        if devp != dev or Q.shape[1] != P.shape[1]:
+            raise _lib.M2dError("ball_query: Q %s on %s and P %s on %s do not go together"
+                                % (tuple(Q.shape), dev, tuple(P.shape), devp))
+        M, D = Q.shape
+        N = P.shape[0]
+        if r2 is not None and (_chk(r2) != dev or tuple(r2.shape) != (N,)):
+            raise _lib.M2dError("ball_query: r2 (%d,) on %s expected, got %s on %s" % (N, dev, tuple(r2.shape), r2.device))
+        count = None if r2 is None else torch.empty((M,), dtype=torch.int32, device=dev)
+        nn_d2 = torch.empty((M,), dtype=torch.float32, device=dev)
+        nn_idx = torch.empty((M,), dtype=torch.int32, device=dev)
+        ws, nws = _workspace(dev, "m2d_ball_query_workspace_bytes", M, N)
+        _launch("m2d_ball_query", dev, _ptr(Q), ldq, M, _ptr(P), ldp, N, D, _ptr(r2), _ptr(count), _ptr(nn_d2),
+                _ptr(nn_idx), _ptr(ws), nws)
+        return count, nn_d2, nn_idx
+
     def dropout(self, x, mask, p_keep=0.5, scale=2.0, seed=None, offset=0, out=None):
         """y = x * keep * scale. seed None: keep from the uint8 `mask` (the caller's); else Philox4x32-10 bits of
         (seed, offset, index), written into `mask` when given. x None: the mask only. -> y (or mask)."""

@@ -22,6 +22,15 @@ has the distribution of the real ones, as the FID_k / Div_k of AIST++ and the FI
     moments  -> Frechet distance (m2d_frechet: two Jacobi eigen-solves, m2d_sym_eig's kernel, and two products)
     features -> mean pairwise distance (m2d_pairwise_mean_dist): diversity (one group), multimodality (a group per
                 piece of music)
+
+k-nearest-neighbour scores (include/m2d.h "nearest-neighbour queries") separate what one Frechet
+number mixes - fidelity from variety - and ask whether a generator has memorised its training rows: improved
+precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020) and nearest-training-row
+distances:
+
+    rows        -> k-th nearest-neighbour radii inside a set (m2d_knn_radii)
+    rows, radii -> per query: in how many balls it lies, and its nearest row of the other set (m2d_ball_query)
+    both        -> prdc(real, fake, k)
 """
 import numpy as np
 import torch
@@ -205,3 +214,68 @@ def standardize(X, mean, cov):
     var = torch.diagonal(cov)
     sd = torch.where(var > 0, var.sqrt(), torch.ones_like(var))
     return ((X.double() - mean) / sd).float().contiguous()
+
+
+# ------------------------------------------------------------------------------------ k-nearest-neighbour scores
+PRDC_KEYS = ("precision", "recall", "density", "coverage", "nn_ratio_median", "nn_fake_to_real_median",
+             "nn_real_to_real_median")
+
+
+def knn_radii(X, k=5):
+    """X (N, D) fp32, N >= k + 1 -> r2 (N,) fp32: the k-th smallest SQUARED distance of row i to the rows j != i (the
+    row itself is excluded by index; a duplicate of it counts). d2 = sum_d (x_d - y_d)^2, one fp32 fma chain."""
+    return kernels.impl().knn_radii(X, int(k))
+
+
+def ball_query(Q, P, r2=None):
+    """Q (M, D), P (N, D) fp32, r2 (N,) or None -> (count (M,) int32 or None, nn_d2 (M,) fp32, nn_idx (M,) int32):
+    count[j] = #{i : d2(Q_j, P_i) <= r2[i]}, nn_d2[j] = min_i d2(Q_j, P_i), nn_idx[j] the smallest i attaining it"""
+    return kernels.impl().ball_query(Q, P, r2)
+
+
+def _median64(x):
+    s = torch.sort(x.double()).values
+    n = s.numel()
+    return 0.5 * (s[(n - 1) // 2] + s[n // 2])
+
+
+def nearest_stats(d2):
+    """d2 (n,) squared distances -> {'median', 'mean', 'min'} of their square roots, fp64 0-dim tensors on d2's device
+    (the median of an even number of values is the mean of the two middle ones)"""
+    d = d2.double().sqrt()
+    return {"median": _median64(d), "mean": d.mean(), "min": d.min()}
+
+
+def prdc(real, fake, k=5):
+    """real (N, D), fake (M, D) fp32 rows, N, M >= k + 1 -> dict of fp64 0-dim device tensors (PRDC_KEYS). With
+    r2_R[i] / r2_F[j] the k-th nearest-neighbour radii inside each set:
+        precision = mean_j [exists i: d2(F_j, R_i) <= r2_R[i]]      density  = sum_j #{i: d2(F_j, R_i) <= r2_R[i]} / (k M)
+        recall    = mean_i [exists j: d2(R_i, F_j) <= r2_F[j]]      coverage = mean_i [min_j d2(R_i, F_j) <= r2_R[i]]
+        nn_fake_to_real_median = median_j sqrt(min_i d2(F_j, R_i)), nn_real_to_real_median = median_i sqrt(r2_R[i] at k = 1)
+        nn_ratio_median = their quotient (NaN when the denominator is 0): well below 1, the generated rows sit closer to
+        real rows than real rows sit to each other - memorisation.
+    Two radii launches, the k = 1 radii and two queries (the real-to-fake query gives both the recall counts and the
+    minima coverage needs); the means are integer torch reductions of the (M,) / (N,) results (the density sum in int64) and one division. No host
+    read inside."""
+    k = int(k)
+    r2_real = knn_radii(real, k)
+    r2_fake = knn_radii(fake, k)
+    r2_real1 = r2_real if k == 1 else knn_radii(real, 1)
+    cnt_f, nn_f, _ = ball_query(fake, real, r2_real)
+    cnt_r, nn_r, _ = ball_query(real, fake, r2_fake)
+    f2r = nearest_stats(nn_f)["median"]
+    r2r = nearest_stats(r2_real1)["median"]
+    nan = torch.full_like(r2r, float("nan"))
+    # integer counts, then ONE fp64 division each, by a device tensor (a division by a Python number is carried out as a
+    # multiplication by its reciprocal on the device, which rounds twice)
+    def ratio(count, n):
+        return count.double() / torch.full((), float(n), dtype=torch.float64, device=count.device)
+
+    n_real, n_fake = real.shape[0], fake.shape[0]
+    return {"precision": ratio((cnt_f > 0).sum(), n_fake),
+            "recall": ratio((cnt_r > 0).sum(), n_real),
+            "density": ratio(cnt_f.long().sum(), k * n_fake),
+            "coverage": ratio((nn_r <= r2_real).sum(), n_real),
+            "nn_ratio_median": torch.where(r2r > 0, f2r / torch.where(r2r > 0, r2r, torch.ones_like(r2r)), nan),
+            "nn_fake_to_real_median": f2r,
+            "nn_real_to_real_median": r2r}

@@ -2,7 +2,7 @@
 
     python -m music2dance_amd.phase3.evaluate -c music2dance_amd/phase3/configs/default.yaml -l <logdir> \
         --classifier logs/type2/weights.pt [--gen-weights PATH] [--repeats 20] [--synthetic] [--beat-align] \
-        [--frechet [--modes K]]
+        [--frechet [--modes K] [--prdc [K]]]
 
 1. Jerkiness (losses.jerkiness) of every real validation take and of the dance generated from its music, on
    inverse-MinMax-scaled poses: mean and unbiased standard deviation of each.
@@ -30,6 +30,11 @@ sampling floor `fd_kinetic` is to be read against), `div_kinetic_real`, `div_kin
 `fd_kinetic_converged` and `kinetic_dims`. --modes K (K >= 2, needs --frechet) runs the generator K times on the same
 audio slices, fresh noise each time, and adds `multimodality_kinetic`: the mean pairwise distance among the K dances
 of a slice, averaged over the slices. A value that needs more rows than there are is `null`.
+
+--prdc [K] (default 5, needs --frechet) adds the k-nearest-neighbour scores of DESIGN.md section 15 (metrics.prdc) on the
+same standardised kinetic features, real rows against generated rows: `precision_kinetic`, `recall_kinetic`,
+`density_kinetic`, `coverage_kinetic`, `nn_ratio_median_kinetic`, `nn_fake_to_real_median_kinetic`,
+`nn_real_to_real_median_kinetic` and `prdc_k`; `null` with fewer than K + 1 rows.
 """
 import argparse
 import glob
@@ -65,9 +70,16 @@ def parse_args(argv=None):
                                                            "kinetic features of the real and the generated dances")
     ap.add_argument("--modes", type=int, default=None, help="with --frechet: generate K >= 2 dances per audio slice "
                                                             "and score their multimodality")
+    ap.add_argument("--prdc", type=int, nargs="?", const=5, default=None,
+                    help="with --frechet: k-nearest-neighbour precision, recall, density and coverage of the kinetic "
+                         "features, K neighbours (default 5)")
     opts = ap.parse_args(argv)
     if opts.modes is not None and not opts.frechet:
         ap.error("--modes requires --frechet")
+    if opts.prdc is not None and not opts.frechet:
+        ap.error("--prdc requires --frechet")
+    if opts.prdc is not None and opts.prdc < 1:
+        ap.error("--prdc needs K >= 1")
     if opts.modes is not None and opts.modes < 2:
         ap.error("--modes needs K >= 2")
     return opts
@@ -127,11 +139,12 @@ def beat_rows(audio, real_i, fake_i, hop, rate):
     return out
 
 
-def kinetic_rows(real_i, fakes_i, fps, up_axis=1):
+def kinetic_rows(real_i, fakes_i, fps, up_axis=1, prdc_k=None):
     """The keys of --frechet (and, for more than one generated set, of --modes): real_i (N, T, 69) and the list fakes_i
     of generated sets of the same shape, inverse-scaled; set k row n is the k-th dance made for the music of real row
     n. Features are standardised by the real set's moments; both Frechet pairs go through ONE m2d_frechet call. The
-    only host reads are the final scalars."""
+    only host reads are the final scalars. prdc_k (--prdc): also metrics.prdc of the standardised real rows against
+    the first generated set with that many neighbours, keys suffixed `_kinetic`, and `prdc_k`."""
     from .. import metrics
     nan = float("nan")
     N = real_i.shape[0]
@@ -141,6 +154,9 @@ def kinetic_rows(real_i, fakes_i, fps, up_axis=1):
            "fd_kinetic_converged": None, "kinetic_dims": int(Fr.shape[1])}
     if len(fakes_i) > 1:
         res["multimodality_kinetic"] = nan
+    if prdc_k is not None:
+        res.update({"%s_kinetic" % key: nan for key in metrics.PRDC_KEYS})
+        res["prdc_k"] = int(prdc_k)
     if N < 2:
         return res
     mean, cov = metrics.feature_moments(Fr)
@@ -160,6 +176,9 @@ def kinetic_rows(real_i, fakes_i, fps, up_axis=1):
     if len(Zf) > 1:
         Z = torch.stack(Zf, 1).reshape(N * len(Zf), -1).contiguous()       # the dances of a slice are consecutive rows
         res["multimodality_kinetic"] = float(metrics.mean_pairwise_distance(Z, groups=N).mean().cpu())
+    if prdc_k is not None and N >= prdc_k + 1:
+        for key, val in metrics.prdc(Zr, Zf[0], prdc_k).items():
+            res["%s_kinetic" % key] = float(val.cpu())
     return res
 
 
@@ -276,7 +295,8 @@ def evaluate(opts, cfg, device):
         # the scores above are made of
         more = [scaler.inverse_transform_device(gen(slices, [T] * N).reshape(N, T, STICK_CHANNELS).contiguous())
                 for _ in range((getattr(opts, "modes", None) or 1) - 1)]
-        kinetic = kinetic_rows(real_i, [fake_i] + more, float(cfg["dataset"]["video_rate"]))
+        kinetic = kinetic_rows(real_i, [fake_i] + more, float(cfg["dataset"]["video_rate"]),
+                               prdc_k=getattr(opts, "prdc", None))
     return summary(real_jerk.cpu().numpy(), fake_jerk.cpu().numpy(), real_pred.cpu().numpy(),
                    fake_pred.cpu().numpy(), beat=beat, kinetic=kinetic)
 
