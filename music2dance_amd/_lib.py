@@ -7,6 +7,8 @@ tensor on a HIP device, the wrapper raises.
 import ctypes
 import os
 
+from . import levers
+
 _c = ctypes
 _F = _c.c_void_p   # const float* / float*  (device pointers travel as integers)
 _I = _c.c_int
@@ -14,7 +16,7 @@ _S = _c.c_size_t
 _f = _c.c_float
 _L = _c.c_long
 
-LIB_PATH = os.environ.get("M2D_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
+LIB_PATH = levers.value("M2D_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
                                                       "libm2d_hip.so")
 
 class AdamItem(_c.Structure):

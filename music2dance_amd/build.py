@@ -9,6 +9,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from . import levers
+
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
@@ -19,7 +21,7 @@ SOURCES = ["m2d_runtime.hip", "gemm_engine.hip", "conv1d.hip", "tcn.hip", "probe
 STAMPED = ["gemm_engine.hip", "tcn.hip"]
 STAMP_LIB_PATH = os.path.join(LIB_DIR, "libm2d_hip_stamp.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
-         "-Wno-unused-function"] + os.environ.get("M2D_EXTRA_FLAGS", "").split()
+         "-Wno-unused-function"] + levers.value("M2D_EXTRA_FLAGS", "").split()
 
 
 def _hipcc():

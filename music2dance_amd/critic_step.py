@@ -40,11 +40,10 @@ pass's activation and gradient buffers between its sections. `_Grads` binds p.gr
 `GanCriticStep` and `CondCriticStep` are schedules of their own over a `PoseBranch`.
 """
 import contextlib
-import os
 
 import torch
 
-from . import kernels, ops
+from . import kernels, levers, ops
 
 ACT_NONE, ACT_RELU = ops.ACT_NONE, ops.ACT_RELU
 K = kernels.impl
@@ -326,7 +325,7 @@ class CriticStep:
         self.overlap = self.audio is not None and getattr(type(critic), "overlap_branches", True)
         # the penalty's first backward and the score backward of the audio branch as ONE 2B-row launch per layer
         # (M2D_MERGE_AUDIO_BWD=0: two B-row chains, the round-4 schedule)
-        self.merge_audio_chains = os.environ.get("M2D_MERGE_AUDIO_BWD", "1") != "0"
+        self.merge_audio_chains = levers.on("M2D_MERGE_AUDIO_BWD")
         self._side = None
         self.join_pairs = None   # diagnostics (engine.timed_wait): how long the pose branch waited for the generator forward
 

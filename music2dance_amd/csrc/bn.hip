@@ -293,7 +293,7 @@ static int launch_reduce(BnReduceArgs& a, hipStream_t stream) {
   if (nsplit < 1) nsplit = 1;
   a.rows_per_block = m2d_ceil_div(a.B, nsplit);
   {
-    static const bool on = [] { const char* e = getenv("M2D_BN_VEC_ROWS"); return !(e && e[0] == '0'); }();   // A/B lever
+    static const bool on = m2d_env_on("M2D_BN_VEC_ROWS");   // A/B lever
     const uintptr_t al = (uintptr_t)a.x | (uintptr_t)(a.mode == 1 ? a.dy : a.x) | (uintptr_t)((a.mode == 2 && a.mask) ? a.mask : a.x);
     a.vec_rows = (on && a.cpb > 1 && (a.L & 3) == 0 && (al & 15u) == 0) ? 1 : 0;
   }
@@ -687,7 +687,7 @@ static BnApplyArgs bn_apply_args(const float* x, const float* gamma, const float
 }
 
 static bool bn_fin_in_apply() {   // A/B lever (0: the separate m2d_bn_finalize_fwd_kernel launch of rounds 1-5)
-  static const bool on = [] { const char* e = getenv("M2D_BN_FIN_IN_APPLY"); return !(e && e[0] == '0'); }();
+  static const bool on = m2d_env_on("M2D_BN_FIN_IN_APPLY");
   return on;
 }
 

@@ -1,27 +1,15 @@
 // Label conditioning and dropout of the conditional phase-2 networks (phase2/archis/conditional.py):
 //   * [x | E[label]] concatenation, batch-first for the generator's GRU input and channels-first for the critic
-//   * the labelled variant of m2d_pose_pack3: the critic's [interpolated | real | fake] rows with their label channels
+//   * m2d_pose_pack3 and its labelled variant: the critic's [interpolated | real | fake] rows, with their label channels
 //   * the embedding-table gradient: a fixed-order fp64 sum, one workgroup per (class, column), no atomics
 //   * dropout y = x * keep * scale from a caller's byte mask or from Philox4x32-10 bits made on the device
 //   * standard normals indexed by absolute frame (the streaming generator's noise, phase3/generate.py)
 // Labels are int64 (torch's default index type). A label outside [0, L) never indexes the table: the features it would
 // have selected (forward) or the whole table gradient (backward) become NaN, so the loss shows it.
 #include "m2d_common.h"
+#include "m2d_reduce.h"
 
 namespace {
-
-__device__ __forceinline__ double cond_block_sum_256(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) sh[t] += sh[t + s];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
 
 __device__ __forceinline__ float label_feature(const float* E, const long long* labels, int b, int d, int L, int D) {
   const long long l = labels[b];
@@ -53,18 +41,35 @@ __global__ void __launch_bounds__(256) m2d_label_concat_kernel(const float* __re
   }
 }
 
-// m2d_pose_pack3's tile transpose (poses through LDS, 128-byte runs along time out), plus D label channels per row
-#define M2D_PACKL_TT 32
-__global__ void __launch_bounds__(256) m2d_pose_pack3_label_kernel(
-    const float* __restrict__ real, const float* __restrict__ fake, const float* __restrict__ alpha,
-    const float* __restrict__ E, const long long* __restrict__ real_lbl, const long long* __restrict__ fake_lbl,
-    float* __restrict__ out, int B, int T, int C, int L, int D) {
+// ---------------------------------------------------------------- critic-iteration input pack
+// The critic iteration's three pose batches in ONE channels-first buffer (3B, C + D, T) - [interpolated | real | fake] -
+// from the loader's real poses (B, T, C) and the generator's rows (B*T, C) (phase3/train.py:196-199 permute +
+// contiguous, losses.py:13-25 interpolate): a (32 frames x C joints) tile is read as one contiguous run, staged in
+// LDS, and leaves as 128-byte runs along time per joint row. The interpolation is the reference's expression,
+// three separately rounded fp32 operations. LABELS: D label channels E[label] follow the C pose channels of every row
+// (the interpolated rows carry the real labels); without them D = 0 and the struct is empty.
+#define M2D_PACK_TT 32
+template <bool LABELS>
+struct PackLabels {};
+template <>
+struct PackLabels<true> {
+  const float* E;
+  const long long* real_lbl;
+  const long long* fake_lbl;
+  int L, D;
+};
+
+template <bool LABELS>
+__global__ void __launch_bounds__(256) m2d_pose_pack3_kernel(const float* __restrict__ real,
+                                                             const float* __restrict__ fake,
+                                                             const float* __restrict__ alpha, float* __restrict__ out,
+                                                             int B, int T, int C, PackLabels<LABELS> lab) {
   extern __shared__ float sh[];  // [2][TT][C + 1]
-  const int b = blockIdx.y, t0 = blockIdx.x * M2D_PACKL_TT;
-  const int nt = min(M2D_PACKL_TT, T - t0);
+  const int b = blockIdx.y, t0 = blockIdx.x * M2D_PACK_TT;
+  const int nt = min(M2D_PACK_TT, T - t0);
   const int ld = C + 1;
   float* sr = sh;
-  float* sf = sh + M2D_PACKL_TT * ld;
+  float* sf = sh + M2D_PACK_TT * ld;
   const size_t base = ((size_t)b * T + t0) * C;
   for (int i = threadIdx.x; i < nt * C; i += 256) {
     const int t = i / C, c = i - t * C;
@@ -74,13 +79,14 @@ __global__ void __launch_bounds__(256) m2d_pose_pack3_label_kernel(
   __syncthreads();
   const float a = alpha[b];
   const float na = __fsub_rn(1.f, a);
-  const int Ct = C + D;
+  int Ct = C;
+  if constexpr (LABELS) Ct = C + lab.D;
   const size_t plane = (size_t)Ct * T;
   float* oi = out + (size_t)b * plane + t0;
   float* orl = out + ((size_t)B + b) * plane + t0;
   float* of = out + ((size_t)2 * B + b) * plane + t0;
-  for (int i = threadIdx.x; i < C * M2D_PACKL_TT; i += 256) {
-    const int c = i / M2D_PACKL_TT, t = i - c * M2D_PACKL_TT;
+  for (int i = threadIdx.x; i < C * M2D_PACK_TT; i += 256) {
+    const int c = i / M2D_PACK_TT, t = i - c * M2D_PACK_TT;
     if (t < nt) {
       const float r = sr[t * ld + c], f = sf[t * ld + c];
       oi[(size_t)c * T + t] = __fadd_rn(__fmul_rn(a, r), __fmul_rn(na, f));
@@ -88,14 +94,16 @@ __global__ void __launch_bounds__(256) m2d_pose_pack3_label_kernel(
       of[(size_t)c * T + t] = f;
     }
   }
-  for (int i = threadIdx.x; i < D * M2D_PACKL_TT; i += 256) {
-    const int d = i / M2D_PACKL_TT, t = i - d * M2D_PACKL_TT;
-    if (t < nt) {
-      const float er = label_feature(E, real_lbl, b, d, L, D);
-      const float ef = label_feature(E, fake_lbl, b, d, L, D);
-      oi[(size_t)(C + d) * T + t] = er;
-      orl[(size_t)(C + d) * T + t] = er;
-      of[(size_t)(C + d) * T + t] = ef;
+  if constexpr (LABELS) {
+    for (int i = threadIdx.x; i < lab.D * M2D_PACK_TT; i += 256) {
+      const int d = i / M2D_PACK_TT, t = i - d * M2D_PACK_TT;
+      if (t < nt) {
+        const float er = label_feature(lab.E, lab.real_lbl, b, d, lab.L, lab.D);
+        const float ef = label_feature(lab.E, lab.fake_lbl, b, d, lab.L, lab.D);
+        oi[(size_t)(C + d) * T + t] = er;
+        orl[(size_t)(C + d) * T + t] = er;
+        of[(size_t)(C + d) * T + t] = ef;
+      }
     }
   }
 }
@@ -128,7 +136,7 @@ __global__ void __launch_bounds__(256) m2d_label_embed_bwd_kernel(const float* _
     for (int t = threadIdx.x; t < T; t += 256)
       acc += (double)(layout == 0 ? dx[row + (size_t)t * Ctot + c] : dx[row + (size_t)c * T + t]);
   }
-  acc = cond_block_sum_256(acc, sh);
+  acc = m2d_block_sum<256>(acc, sh);
   if (threadIdx.x == 0) dE[blockIdx.x] = (float)acc;
 }
 
@@ -231,6 +239,21 @@ int m2d_label_concat(const float* x, const float* E, const long long* labels, fl
   return M2D_OK;
 }
 
+// [interpolated | real | fake] poses channels-first (3B, C, T) from real (B, T, C), fake rows (B*T, C), alpha (B,):
+// replaces permute(0,2,1).contiguous() x2 (phase3/train.py:196-199), the interpolation (losses.py:13-25) and the
+// concatenation of the batches the critic scores in one pass.
+int m2d_pose_pack3(const float* real, const float* fake, const float* alpha, float* out, int B, int T, int C,
+                   void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0 || T <= 0 || C <= 0 || C > 1024) M2D_FAIL(M2D_ERR_ARG, "m2d_pose_pack3: bad shape");
+  M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 20.0 * (double)B * T * C, "pose_pack3");
+  const size_t lds = 2 * (size_t)M2D_PACK_TT * (C + 1) * sizeof(float);
+  hipLaunchKernelGGL(m2d_pose_pack3_kernel<false>, dim3(m2d_ceil_div(T, M2D_PACK_TT), B), dim3(256), lds, stream, real,
+                     fake, alpha, out, B, T, C, PackLabels<false>{});
+  M2D_CHECK_LAUNCH("m2d_pose_pack3");
+  return M2D_OK;
+}
+
 int m2d_pose_pack3_label(const float* real, const float* fake, const float* alpha, const float* E,
                          const long long* real_lbl, const long long* fake_lbl, float* out, int B, int T, int C, int L,
                          int D, void* stream_) {
@@ -239,9 +262,9 @@ int m2d_pose_pack3_label(const float* real, const float* fake, const float* alph
       !fake_lbl || !out)
     M2D_FAIL(M2D_ERR_ARG, "m2d_pose_pack3_label: bad arguments");
   M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 4.0 * (double)B * T * (5 * C + 3 * D), "pose_pack3_label");
-  const size_t lds = 2 * (size_t)M2D_PACKL_TT * (C + 1) * sizeof(float);
-  hipLaunchKernelGGL(m2d_pose_pack3_label_kernel, dim3(m2d_ceil_div(T, M2D_PACKL_TT), B), dim3(256), lds, stream, real,
-                     fake, alpha, E, real_lbl, fake_lbl, out, B, T, C, L, D);
+  const size_t lds = 2 * (size_t)M2D_PACK_TT * (C + 1) * sizeof(float);
+  hipLaunchKernelGGL(m2d_pose_pack3_kernel<true>, dim3(m2d_ceil_div(T, M2D_PACK_TT), B), dim3(256), lds, stream, real,
+                     fake, alpha, out, B, T, C, PackLabels<true>{E, real_lbl, fake_lbl, L, D});
   M2D_CHECK_LAUNCH("m2d_pose_pack3_label");
   return M2D_OK;
 }

@@ -152,16 +152,16 @@ __global__ void __launch_bounds__(256) m2d_pack_weights_subpixel_kernel(const fl
 // 67 TFLOP/s, the worst large launch of the step. Cost: ceil(ks / s) * s tap slots instead of ks (k25 / s4: 28, + 12 %).
 static inline bool subpixel_tall(int Cin, int Cout, int ks, int stride);
 static inline bool bwd_subpixel(int Cin, int Cout, int ks, int stride, bool masked_dy = false) {
-  static const bool on = [] { const char* e = getenv("M2D_SUBPIXEL"); return !(e && e[0] == '0'); }();
-  static const int max_rows = [] { const char* e = getenv("M2D_SUBPIXEL_MAXROWS"); return e ? atoi(e) : 128; }();  // A/B lever
-  static const int tall_max_cin = [] { const char* e = getenv("M2D_SUBPIXEL_TALL_MAXCIN"); return e ? atoi(e) : 64; }();  // A/B lever (measured: 64 -> 128 layer 658 -> 587 us, the 128- and 256-channel layers lose 7 - 12 %)
+  static const bool on = m2d_env_on("M2D_SUBPIXEL");
+  static const int max_rows = m2d_env_int("M2D_SUBPIXEL_MAXROWS", 128);  // A/B lever
+  static const int tall_max_cin = m2d_env_int("M2D_SUBPIXEL_TALL_MAXCIN", 64);  // A/B lever (measured: 64 -> 128 layer 658 -> 587 us, the 128- and 256-channel layers lose 7 - 12 %)
   if (on && !masked_dy && Cin > 32 && Cin <= tall_max_cin && subpixel_tall(Cin, Cout, ks, stride)) return true;
   return on && stride > 1 && Cin * stride <= max_rows && Cin * stride >= 64 && Cout >= 16 && ks > stride;
 }
 // ... and without the phantom taps of the last slot where the tile is exactly the four phases of 32 channels (the audio
 // critic's 32 -> 64 layer, the WaveGAN encoder's): M2D_SUBPIXEL_TALL=0 keeps the (ci, r) order
 static inline bool subpixel_tall(int Cin, int Cout, int ks, int stride) {
-  static const bool on = [] { const char* e = getenv("M2D_SUBPIXEL_TALL"); return !(e && e[0] == '0'); }();
+  static const bool on = m2d_env_on("M2D_SUBPIXEL_TALL");
   const int nt = (ks + stride - 1) / stride;
   // (the phase-major image is readable by m2d_gemm_dl_tall_kernel only: with M2D_DL=0 the (ci, r) order stays - ADVICE r5)
   return on && m2d_dl_enabled() && Cin % 32 == 0 && stride == 4 && ks - stride * (nt - 1) == 1 && nt >= 2;
@@ -339,7 +339,7 @@ static inline int k4_groups(int ks, int pad) { return (ks + k4_shift(pad) + 3) /
 // blocks of four (M2D_K4_PAIR=0: A/B lever)
 static inline int k4_nlast(int ks, int pad) { return ks + k4_shift(pad) - 4 * (k4_groups(ks, pad) - 1); }
 static inline int k4_paired(int Cin, int ks, int pad) {
-  static const bool on = [] { const char* e = getenv("M2D_K4_PAIR"); return !(e && e[0] == '0'); }();
+  static const bool on = m2d_env_on("M2D_K4_PAIR");
   // (the kernel's partial-group loops are instantiated for slots [1, 4) and [0, 2): k25 / pad 11, every layer that takes this path)
   return on && (Cin % 4) == 0 && k4_groups(ks, pad) >= 4 && k4_shift(pad) == 1 && k4_nlast(ks, pad) == 2;
 }
@@ -381,7 +381,7 @@ extern "C" {
 // (k25: 12 %), and the wide layers' gathers were already served from L1 by the generic engine.
 int m2d_conv1d_k4_applicable(int Cin, int L, int Cout, int ks, int stride, int pad) {
   const int Lout = conv_out_len(L, ks, stride, pad);
-  static const int max_cin = [] { const char* e = getenv("M2D_K4_MAXCIN"); return e ? atoi(e) : 64; }();  // A/B lever
+  static const int max_cin = m2d_env_int("M2D_K4_MAXCIN", 64);  // A/B lever
   return stride == 4 && (L % 4) == 0 && (Cin % 4) == 0 && Cin >= 16 && Cin <= max_cin && Cout >= 64 && Lout > 1 && ks >= 4 &&
          k4_groups(ks, pad) >= 2;
 }

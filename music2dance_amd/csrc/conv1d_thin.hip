@@ -642,7 +642,7 @@ size_t m2d_thin_fwd_stats_ws(int B, int Lout) { return thin_fwd_stats_part(B, Lo
 // workgroups of the persistent forward: one full-occupancy round (8 per CU: 18 KB of LDS, 35-50 registers), fewer when
 // there are not that many groups of four tiles. M2D_THIN_WG_PER_CU: A/B lever
 static int thin_fwd_grid(int total_tiles) {
-  static const int per_cu = [] { const char* e = getenv("M2D_THIN_WG_PER_CU"); const int v = e ? atoi(e) : THIN_WPE; return v >= 1 && v <= 16 ? v : THIN_WPE; }();
+  static const int per_cu = [] { const int v = m2d_env_int("M2D_THIN_WG_PER_CU", THIN_WPE); return v >= 1 && v <= 16 ? v : THIN_WPE; }();
   const int need = m2d_ceil_div(total_tiles, 4), full = 256 * per_cu;
   return need < full ? need : full;
 }
@@ -817,7 +817,7 @@ __global__ void __launch_bounds__(512) thin_long_fwd_kernel(const ThinArgs a, in
 }
 
 static bool thin_long_enabled() {
-  static const bool on = [] { const char* e = getenv("M2D_THIN_LONG"); return !(e && e[0] == '0'); }();   // A/B lever
+  static const bool on = m2d_env_on("M2D_THIN_LONG");   // A/B lever
   return on;
 }
 // Conv1d(1, 32, 250, 50, 124) (DefaultAudioEncoder) and Conv1d(1, 32, 160, 4, 79) (UNetAudioEncoder, phase3/archis/

@@ -22,6 +22,7 @@
 // squared off-diagonal norm the sweep met - is at most (2^-50 ||A||_F)^2. The sweep loop runs at most M2D_EIG_SWEEPS (30)
 // times whatever the data: a NaN compares false, such a matrix runs to the cap and comes out as NaN with converged = 0.
 #include "m2d_common.h"
+#include "m2d_reduce.h"
 
 #include <math.h>
 
@@ -33,19 +34,6 @@
 #define M2D_DBL_MAX 1.79769313486231570e308
 
 namespace {
-
-// fixed-order tree over the 256 threads of a workgroup; every thread gets the total
-__device__ double ds_sum256(double* red, double val) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = val;
-  __syncthreads();
-  for (int s = M2D_DS_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // ---- m2d_kinetic_features: one workgroup per (dance, joint) ----------------------------------------------------------
 __global__ void __launch_bounds__(M2D_DS_THREADS)
@@ -71,9 +59,9 @@ m2d_kinetic_kernel(const float* __restrict__ poses, int T, int J, double fps, in
       e += sqrt((a1 * a1 + a2 * a2) + au * au);
     }
   }
-  h = ds_sum256(red, h);
-  v = ds_sum256(red, v);
-  e = ds_sum256(red, e);
+  h = m2d_block_sum<M2D_DS_THREADS>(h, red);
+  v = m2d_block_sum<M2D_DS_THREADS>(v, red);
+  e = m2d_block_sum<M2D_DS_THREADS>(e, red);
   if (threadIdx.x == 0) {
     float* out = F + (size_t)b * 3 * J;
     out[j] = (float)(h / (double)(T - 1));
@@ -90,7 +78,7 @@ m2d_moments_mean_kernel(const float* __restrict__ X, long long ldx, int N, doubl
   const int d = blockIdx.x;
   double acc = 0.0;
   for (int n = threadIdx.x; n < N; n += M2D_DS_THREADS) acc += (double)X[(size_t)n * ldx + d];
-  acc = ds_sum256(red, acc);
+  acc = m2d_block_sum<M2D_DS_THREADS>(acc, red);
   if (threadIdx.x == 0) mean[d] = acc / (double)N;
 }
 
@@ -127,18 +115,6 @@ struct EigShared {
   int flag;
 };
 
-__device__ double eig_sum(double* red, double val) {   // fixed-order tree over the 1024 threads
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = val;
-  __syncthreads();
-  for (int s = M2D_EIG_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // A (P, D, D) -> w (P, D) ascending, vecs (P, D, D) columns (or null), info (P, 2) doubles [sweeps, converged];
 // vt: (P, n, n) scratch for V^T when vecs is wanted
 __global__ void __launch_bounds__(M2D_EIG_THREADS)
@@ -158,7 +134,7 @@ m2d_sym_eig_kernel(const double* __restrict__ A, int D, double* __restrict__ w, 
     fro += x * x;
     if (V) V[e] = r == c ? 1.0 : 0.0;
   }
-  fro = eig_sum(sh.red, fro);
+  fro = m2d_block_sum<M2D_EIG_THREADS>(fro, sh.red);
   const double tol2 = fro * (0x1p-50 * 0x1p-50);
 
   int sweeps = 0, converged = 0;
@@ -312,9 +288,9 @@ m2d_frechet_final_kernel(const double* __restrict__ mean1, const double* __restr
     const double l = w2[(size_t)pr * D + tid];
     rt = sqrt(l < 0.0 ? 0.0 : l);
   }
-  dmu = ds_sum256(red, dmu);
-  tr = ds_sum256(red, tr);
-  rt = ds_sum256(red, rt);
+  dmu = m2d_block_sum<M2D_DS_THREADS>(dmu, red);
+  tr = m2d_block_sum<M2D_DS_THREADS>(tr, red);
+  rt = m2d_block_sum<M2D_DS_THREADS>(rt, red);
   if (tid == 0) {
     double* o = out + (size_t)pr * 6;
     o[0] = (dmu + tr) - 2.0 * rt;
@@ -343,7 +319,7 @@ m2d_pairwise_rows_kernel(const float* __restrict__ X, long long ldx, int K, int 
     }
     acc += sqrt(ss);
   }
-  acc = ds_sum256(red, acc);
+  acc = m2d_block_sum<M2D_DS_THREADS>(acc, red);
   if (threadIdx.x == 0) part[(size_t)g * K + i] = acc;
 }
 
@@ -353,7 +329,7 @@ m2d_pairwise_final_kernel(const double* __restrict__ part, int K, double* __rest
   const int g = blockIdx.x;
   double acc = 0.0;
   for (int i = threadIdx.x; i < K; i += M2D_DS_THREADS) acc += part[(size_t)g * K + i];
-  acc = ds_sum256(red, acc);
+  acc = m2d_block_sum<M2D_DS_THREADS>(acc, red);
   if (threadIdx.x == 0)
     out[g] = K < 2 ? __longlong_as_double(0x7ff8000000000000LL) : acc / (0.5 * (double)K * (double)(K - 1));
 }

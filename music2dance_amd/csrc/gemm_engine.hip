@@ -1775,7 +1775,7 @@ struct PlanCand {
 // which cost model ranks the plans (m2d_plan_model_set; M2D_PLAN_MODEL overrides the default once at load): 4 = the
 // round-4 model (default: best where a loop body's streams overlap - the two-branch phase-3 critic), 5 = chunk-step floor
 // by tile height + splits up to 256 (best where launches run one after the other: phase 2, the pose-only critic)
-static std::atomic<int> g_plan_model{[] { const char* e = getenv("M2D_PLAN_MODEL"); return (e && e[0] == '5') ? 5 : 4; }()};
+static std::atomic<int> g_plan_model{[] { const char* e = m2d_env_raw("M2D_PLAN_MODEL"); return (e && e[0] == '5') ? 5 : 4; }()};
 extern "C" int m2d_plan_model_set(int model) {
   if (model != 4 && model != 5) M2D_FAIL(M2D_ERR_ARG, "m2d_plan_model_set: 4 or 5");
   g_plan_model.store(model, std::memory_order_relaxed);
@@ -1839,9 +1839,9 @@ static int plan_candidates(int M, int N, int nchunks, int phases, bool allow_spl
   // (m2d_plan_model_set, once per process before its first launch): the two-branch step keeps 4, bench.py's c2 / c5 presets
   // and the phase-2 train script select 5.
   const bool model5 = g_plan_model.load(std::memory_order_relaxed) == 5;
-  static const double slab_mul = [] { const char* e = getenv("M2D_SLAB_COST"); return e ? atof(e) : 1.0; }();   // A/B lever
+  static const double slab_mul = m2d_env_double("M2D_SLAB_COST", 1.0);   // A/B lever
   const double lchunk[3] = {1.50, 1.35, 1.20};
-  static const bool rounds_on = [] { const char* e = getenv("M2D_PLAN_ROUNDS"); return !(e && e[0] == '0'); }();
+  static const bool rounds_on = m2d_env_on("M2D_PLAN_ROUNDS");
   const RoundsModel* rm = !rounds_on ? nullptr : kind == M2D_PLAN_BWD_WEIGHT ? &kRoundsBwdW : kind == M2D_PLAN_BWD_DATA ? &kRoundsBwdD : nullptr;
   const long long max_splits = (model5 || rm) ? 256 : 128;
   PlanCand all[40];
@@ -1925,7 +1925,7 @@ M2dGemmPlan m2d_gemm_plan(int M, int N, int nchunks, int phases, bool allow_spli
     if (b > pl.ws_bytes) pl.ws_bytes = b;
   }
 #ifdef M2D_TUNING
-  if (const char* e = getenv("M2D_PLAN")) {  // "bm,splits" (tuning builds only)
+  if (const char* e = m2d_env_raw("M2D_PLAN")) {  // "bm,splits" (tuning builds only)
     int bm = 0, sp = 0;
     if (sscanf(e, "%d,%d", &bm, &sp) == 2) {
       if (bm == 32 || bm == 64 || bm == 128) pl.bm = bm;
@@ -1950,7 +1950,7 @@ static void launch_tile(const M2dGemmParams& p, dim3 grid, hipStream_t stream) {
 
 // M2D_DL=0: keep row-fast / row-fast launches on the register-staging kernel (A/B lever)
 static bool dl_enabled() {
-  static const bool on = [] { const char* e = getenv("M2D_DL"); return !(e && e[0] == '0'); }();
+  static const bool on = m2d_env_on("M2D_DL");
   return on;
 }
 // (for callers that pick a weight packing only the LDS-direct kernels can read: conv1d.hip's phase-major sub-pixel form)
@@ -1966,7 +1966,7 @@ static inline bool dl_eligible(const M2dGemmParams& p, bool akf, bool bkf) {
 
 // M2D_DL8=0: 128-row LDS-direct launches keep four waves per workgroup (A/B lever)
 static bool dl8_enabled() {
-  static const bool on = [] { const char* e = getenv("M2D_DL8"); return !(e && e[0] == '0'); }();
+  static const bool on = m2d_env_on("M2D_DL8");
   return on;
 }
 
@@ -2056,8 +2056,8 @@ struct Plan {
 // split-K in one launch when the stream has tickets for every tile, the slab holds whole-tile images and stays under
 // the buffer-addressing limit (M2D_FUSED_SPLITK=0: never): the tickets, or NULL for the two-launch form
 static unsigned* decide_fused(const M2dGemmParams& p, const PlanQuery& q, int bm, int splits) {
-  static const bool on = [] { const char* e = getenv("M2D_FUSED_SPLITK"); return !(e && e[0] == '0'); }();
-  static const int max_splits = [] { const char* e = getenv("M2D_FUSE_MAX"); return e ? atoi(e) : M2D_FUSE_MAX_SPLITS; }();  // A/B lever
+  static const bool on = m2d_env_on("M2D_FUSED_SPLITK");
+  static const int max_splits = m2d_env_int("M2D_FUSE_MAX", M2D_FUSE_MAX_SPLITS);  // A/B lever
   if (!on || splits <= 1 || splits > max_splits || p.bwd_data || !q.ws) return nullptr;
   const size_t need = m2d_slab_bytes(p.M, p.N, bm, splits);
   if (need > q.ws_bytes || need >= 0x7fffffffULL || ((uintptr_t)q.ws & 15u)) return nullptr;
@@ -2067,7 +2067,7 @@ static unsigned* decide_fused(const M2dGemmParams& p, const PlanQuery& q, int bm
 }
 
 static bool stats_split_enabled() {   // A/B lever
-  static const bool on = [] { const char* e = getenv("M2D_STATS_SPLIT"); return !(e && e[0] == '0'); }();
+  static const bool on = m2d_env_on("M2D_STATS_SPLIT");
   return on;
 }
 
@@ -2104,7 +2104,7 @@ static int select_plan(const M2dGemmParams& p, const PlanQuery& q, Plan* out) {
     M2D_FAIL(M2D_ERR_ARG, "%s: no launch plan", q.what);
   }
 #ifdef M2D_TUNING
-  if (!q.k4 && getenv("M2D_PLAN")) {
+  if (!q.k4 && m2d_env_raw("M2D_PLAN")) {
     const M2dGemmPlan fp = m2d_gemm_plan(p.M, p.N, q.nchunks, q.phases, allow_split, q.small_tile_penalty, q.kind);
     if (fp.splits > 1 && (!q.ws || q.ws_bytes < fp.splits * mn4))
       M2D_FAIL(M2D_ERR_WORKSPACE, "%s: forced plan needs more workspace", q.what);
@@ -2139,18 +2139,18 @@ extern "C" void m2d_debug_select_plan(int launcher, int M, int N, int nchunks, i
 }
 
 static int stats_narrow_fast_default() {   // A/B lever
-  static const int v = [] { const char* e = getenv("M2D_STATS_NARROW_FAST"); return (e && e[0] == '0') ? 0 : 1; }();
+  static const int v = m2d_env_on("M2D_STATS_NARROW_FAST") ? 1 : 0;
   return v;
 }
 // M2D_TILE_MAP=0: tile id = workgroup id (A/B lever)
 static int tile_map_default() {
-  static const int v = [] { const char* e = getenv("M2D_TILE_MAP"); return e ? atoi(e) : 1; }();
+  static const int v = m2d_env_int("M2D_TILE_MAP", 1);
   return v;
 }
 
 // 16-byte epilogue rows (m2d_tile_epilogue, WIDE) when the output map allows it (M2D_WIDE_EPILOGUE=0: never)
 static void decide_wide(M2dGemmParams& p, int splits, const void* ws) {
-  static const bool wide_on = [] { const char* e = getenv("M2D_WIDE_EPILOGUE"); return !(e && e[0] == '0'); }();
+  static const bool wide_on = m2d_env_on("M2D_WIDE_EPILOGUE");
   auto al16 = [](const void* q) { return ((uintptr_t)q & 15u) == 0; };
   const M2dOutMap& o = p.O;
   bool w = wide_on && !p.bwd_data && (p.N % 4) == 0 && o.redirect_col_p1 == 0;

@@ -997,8 +997,7 @@ static GruPersistState* gru_persist_state(bool create = true) {
   if (!create) return g_gru_ps_init[dev] ? &ps : nullptr;
   if (!g_gru_ps_init[dev]) {
     g_gru_ps_init[dev] = true;
-    const char* e = getenv("M2D_PERSISTENT_GRU");
-    if (e && e[0] == '0') return nullptr;  // usable stays false
+    if (!m2d_env_on("M2D_PERSISTENT_GRU")) return nullptr;  // usable stays false
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return nullptr;
     ps.cus = prop.multiProcessorCount;

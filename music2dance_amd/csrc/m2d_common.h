@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #define M2D_OK 0
@@ -77,6 +78,23 @@ __device__ __forceinline__ float m2d_act(float v, int act, float slope) {
 __device__ __forceinline__ float m2d_act_sel(float v, int act, float slope) {
   const float neg = act == 1 ? 0.f : v * slope;
   return (act != 0 && v < 0.f) ? neg : v;
+}
+
+// ---- environment levers (host code; DESIGN.md "Levers" lists every name) -------------------------------------------
+// A switch is on unless its value begins with '0'; a number is its default when the name is unset. Call sites keep the
+// result in a function-local `static const`, so a lever is read once per process, at first use.
+static inline const char* m2d_env_raw(const char* name) { return getenv(name); }   // for a site with a parse of its own
+static inline bool m2d_env_on(const char* name) {
+  const char* e = m2d_env_raw(name);
+  return !(e && e[0] == '0');
+}
+static inline int m2d_env_int(const char* name, int dflt) {
+  const char* e = m2d_env_raw(name);
+  return e ? atoi(e) : dflt;
+}
+static inline double m2d_env_double(const char* name, double dflt) {
+  const char* e = m2d_env_raw(name);
+  return e ? atof(e) : dflt;
 }
 
 static inline int m2d_ceil_div(int a, int b) { return (a + b - 1) / b; }

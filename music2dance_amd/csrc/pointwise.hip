@@ -6,27 +6,14 @@
 //     (phase3/archis/default.py:235-245)
 // Reductions are two-stage and deterministic: per-block fp64 partials, then one block.
 #include "m2d_common.h"
-
-// ---------------------------------------------------------------- block reduce helper
-__device__ __forceinline__ double block_sum_256(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) sh[t] += sh[t + s];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
+#include "m2d_reduce.h"
 
 __global__ void __launch_bounds__(256) m2d_finish_sum_kernel(const double* partial, int n, double scale,
                                                              float* out) {
   __shared__ double sh[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-  s = block_sum_256(s, sh);
+  s = m2d_block_sum<256>(s, sh);
   if (threadIdx.x == 0) out[0] = (float)(s * scale);
 }
 
@@ -150,7 +137,7 @@ __global__ void __launch_bounds__(256) m2d_gp_norm_partial_kernel(const float* g
     }
     acc += (double)s;
   }
-  acc = block_sum_256(acc, sh);
+  acc = m2d_block_sum<256>(acc, sh);
   if (threadIdx.x == 0) partial[(size_t)b * GP_SPLIT + sp] = acc;
 }
 
@@ -169,7 +156,7 @@ __global__ void __launch_bounds__(256) m2d_gp_penalty_kernel(const double* parti
     if (lp && d < 0.f) d = 0.f;
     s += (double)(d * d);
   }
-  s = block_sum_256(s, sh);
+  s = m2d_block_sum<256>(s, sh);
   if (threadIdx.x == 0) out[0] = (float)(s / (double)B);
 }
 
@@ -194,7 +181,7 @@ __global__ void __launch_bounds__(256) m2d_absdiff_partial_kernel(const float* a
   double s = 0.0;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
     s += (double)fabsf(a[i] - b[i]);
-  s = block_sum_256(s, sh);
+  s = m2d_block_sum<256>(s, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -223,7 +210,7 @@ __global__ void __launch_bounds__(256) m2d_tv_partial_kernel(const float* x, int
     const float* p = x + b * sb + c * sc + t * st;
     s += (double)fabsf(p[st] - p[0]);
   }
-  s = block_sum_256(s, sh);
+  s = m2d_block_sum<256>(s, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -268,7 +255,7 @@ __global__ void __launch_bounds__(256) m2d_jerk_partial_kernel(const float* x, i
     const float d = __fsub_rn(__fadd_rn(__fsub_rn(p[3 * st], __fmul_rn(3.f, p[2 * st])), __fmul_rn(3.f, p[st])), p[0]);
     s += (double)__fmul_rn(d, d);
   }
-  s = block_sum_256(s, sh);
+  s = m2d_block_sum<256>(s, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -439,47 +426,6 @@ __global__ void __launch_bounds__(256) m2d_tanh_bwd_bwd_kernel(const float* g, c
     g_y[i] = -2.f * y[i] * g[i] * gy[i];
 }
 
-// ---------------------------------------------------------------- critic-iteration input pack
-// The critic iteration's three pose batches in ONE channels-first buffer (3B, C, T) - [interpolated | real | fake] -
-// from the loader's real poses (B, T, C) and the generator's rows (B*T, C) (phase3/train.py:196-199 permute +
-// contiguous, losses.py:13-25 interpolate): a (32 frames x C joints) tile is read as one contiguous run, staged in
-// LDS, and leaves as 128-byte runs along time per joint row. The interpolation is the reference's expression,
-// three separately rounded fp32 operations.
-#define M2D_PACK_TT 32
-__global__ void __launch_bounds__(256) m2d_pose_pack3_kernel(const float* __restrict__ real,
-                                                             const float* __restrict__ fake,
-                                                             const float* __restrict__ alpha, float* __restrict__ out,
-                                                             int B, int T, int C) {
-  extern __shared__ float sh[];  // [2][TT][C + 1]
-  const int b = blockIdx.y, t0 = blockIdx.x * M2D_PACK_TT;
-  const int nt = min(M2D_PACK_TT, T - t0);
-  const int ld = C + 1;
-  float* sr = sh;
-  float* sf = sh + M2D_PACK_TT * ld;
-  const size_t base = ((size_t)b * T + t0) * C;
-  for (int i = threadIdx.x; i < nt * C; i += 256) {
-    const int t = i / C, c = i - t * C;
-    sr[t * ld + c] = real[base + i];
-    sf[t * ld + c] = fake[base + i];
-  }
-  __syncthreads();
-  const float a = alpha[b];
-  const float na = __fsub_rn(1.f, a);
-  const size_t plane = (size_t)C * T;
-  float* oi = out + (size_t)b * plane + t0;
-  float* orl = out + ((size_t)B + b) * plane + t0;
-  float* of = out + ((size_t)2 * B + b) * plane + t0;
-  for (int i = threadIdx.x; i < C * M2D_PACK_TT; i += 256) {
-    const int c = i / M2D_PACK_TT, t = i - c * M2D_PACK_TT;
-    if (t < nt) {
-      const float r = sr[t * ld + c], f = sf[t * ld + c];
-      oi[(size_t)c * T + t] = __fadd_rn(__fmul_rn(a, r), __fmul_rn(na, f));
-      orl[(size_t)c * T + t] = r;
-      of[(size_t)c * T + t] = f;
-    }
-  }
-}
-
 // loss scalars of a critic iteration from the (3B,) scores [interpolated | real | fake] and the penalty term(s):
 // out[0] = E[D(fake)] - E[D(real)] + gamma * gp, out[1] = gp, out[2] = E[D(fake)] - E[D(real)]
 // (phase3/train.py:204-212, phase2/train.py:146-153). One block; fp64 accumulation.
@@ -491,8 +437,8 @@ __global__ void __launch_bounds__(256) m2d_wgan_critic_loss_kernel(const float* 
     sr += (double)scores[B + i];
     sf += (double)scores[2 * B + i];
   }
-  sr = block_sum_256(sr, sh);
-  sf = block_sum_256(sf, sh);
+  sr = m2d_block_sum<256>(sr, sh);
+  sf = m2d_block_sum<256>(sf, sh);
   if (threadIdx.x == 0) {
     const float er = (float)(sr / B), ef = (float)(sf / B);
     const float gp = pen1 ? __fadd_rn(pen0[0], pen1[0]) : pen0[0];
@@ -537,8 +483,8 @@ __global__ void __launch_bounds__(256) m2d_bce_logits_fwd_kernel(const float* __
     s1 += bce_elem(v, t1);
     if (dx) dx[n0 + i] = (float)((bce_sigmoid(v) - (double)t1) * inv1);
   }
-  s0 = block_sum_256(s0, sh);
-  s1 = block_sum_256(s1, sh);
+  s0 = m2d_block_sum<256>(s0, sh);
+  s1 = m2d_block_sum<256>(s1, sh);
   if (threadIdx.x == 0) {
     const double m0 = s0 * inv0, m1 = n1 > 0 ? s1 * inv1 : 0.0;
     out[0] = (float)(m0 + m1);
@@ -993,21 +939,6 @@ int m2d_tanh_bwd_bwd(const float* g, const float* gy, const float* y, float* g_y
   return M2D_OK;
 }
 
-// [interpolated | real | fake] poses channels-first (3B, C, T) from real (B, T, C), fake rows (B*T, C), alpha (B,):
-// replaces permute(0,2,1).contiguous() x2 (phase3/train.py:196-199), the interpolation (losses.py:13-25) and the
-// concatenation of the batches the critic scores in one pass.
-int m2d_pose_pack3(const float* real, const float* fake, const float* alpha, float* out, int B, int T, int C,
-                   void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (B <= 0 || T <= 0 || C <= 0 || C > 1024) M2D_FAIL(M2D_ERR_ARG, "m2d_pose_pack3: bad shape");
-  M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 20.0 * (double)B * T * C, "pose_pack3");
-  const size_t lds = 2 * (size_t)M2D_PACK_TT * (C + 1) * sizeof(float);
-  hipLaunchKernelGGL(m2d_pose_pack3_kernel, dim3(m2d_ceil_div(T, M2D_PACK_TT), B), dim3(256), lds, stream, real, fake,
-                     alpha, out, B, T, C);
-  M2D_CHECK_LAUNCH("m2d_pose_pack3");
-  return M2D_OK;
-}
-
 // out[0..2] = (loss_critic, gp, w_dist) from scores (3B,) = [interpolated | real | fake] and the penalty term(s)
 // pen0 (+ pen1, optional: the audio term, losses.py:56-60).
 int m2d_wgan_critic_loss(const float* scores, int B, const float* pen0, const float* pen1, float gamma, float* out,
@@ -1066,6 +997,12 @@ int m2d_maxpool2_bwd(const float* x, const float* dy, float* dx, size_t rows, in
 }
 
 // nn.Upsample(scale_factor=2, mode="linear", align_corners=False) (phase3/archis/default.py:236)
+// M2D_UPSAMPLE_FLAT=0: never the flat 16-byte kernels, forward or backward (A/B lever)
+static bool upsample_flat_on() {
+  static const bool on = m2d_env_on("M2D_UPSAMPLE_FLAT");
+  return on;
+}
+
 // x (B, C, L) -> y: sample b's channels at y + b * y_batch_stride (y_batch_stride 0 or C * 2L: dense (B, C, 2L)); a larger
 // stride writes into a channel block of a wider buffer (the U-Net's skip concatenation made in place)
 int m2d_upsample2_fwd_to(const float* x, float* y, size_t B, int C, int L, long long y_batch_stride, void* stream_) {
@@ -1077,7 +1014,7 @@ int m2d_upsample2_fwd_to(const float* x, float* y, size_t B, int C, int L, long 
   const int Cp = dense ? 0 : C;
   const long long yp = dense ? 0 : y_batch_stride;
   M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 12.0 * rows * (double)L, "upsample2_fwd");
-  static const bool flat_on = [] { const char* e = getenv("M2D_UPSAMPLE_FLAT"); return !(e && e[0] == '0'); }();   // A/B lever
+  const bool flat_on = upsample_flat_on();
   const size_t per_sample = (size_t)C * L;
   if (flat_on && (per_sample & 1) == 0 && per_sample < (1u << 30) && (((uintptr_t)x | (uintptr_t)y) & 15u) == 0 && (yp & 3) == 0 &&
       true) {
@@ -1108,7 +1045,7 @@ int m2d_upsample2_bwd(const float* dy, float* dx, size_t rows, int L, void* stre
   hipStream_t stream = (hipStream_t)stream_;
   if (rows == 0 || L <= 0) M2D_FAIL(M2D_ERR_ARG, "m2d_upsample2_bwd: bad shape");
   M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 12.0 * rows * (double)L, "upsample2_bwd");
-  static const bool flat_on = [] { const char* e = getenv("M2D_UPSAMPLE_FLAT"); return !(e && e[0] == '0'); }();   // A/B lever
+  const bool flat_on = upsample_flat_on();
   if (flat_on && ((rows * (size_t)L) & 3) == 0 && (((uintptr_t)dy | (uintptr_t)dx) & 15u) == 0)
     hipLaunchKernelGGL(m2d_upsample2_bwd_flat_kernel, dim3(grid_for(rows * L / 4, 16384)), dim3(256), 0, stream, dy, dx,
                        rows * L / 4, L);

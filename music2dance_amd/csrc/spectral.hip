@@ -28,6 +28,7 @@
 // Frame t's value depends on t, its samples, the basis and the bands only: the tile size F is a function of (hop, n_fft,
 // nb), the lane a frame lands in changes no operation. No atomics.
 #include "m2d_common.h"
+#include "m2d_reduce.h"
 
 #include <limits.h>
 #include <math.h>
@@ -201,18 +202,6 @@ __global__ void m2d_motion_speed_kernel(const float* __restrict__ p, long long r
 #define BA_NEG (-(1 << 30))
 #define BA_BIG (1 << 20)
 
-__device__ double ba_sum(double* redd, double val) {   // fixed-order tree; every thread gets the total
-  const int tid = threadIdx.x;
-  __syncthreads();
-  redd[tid] = val;
-  __syncthreads();
-  for (int s = M2D_BA_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) redd[tid] += redd[tid + s];
-    __syncthreads();
-  }
-  return redd[0];
-}
-
 __device__ void ba_scan_max(int* sc) {   // inclusive, over the M2D_BA_THREADS entries; callers sync before writing sc
   const int tid = threadIdx.x;
   __syncthreads();
@@ -251,7 +240,7 @@ __device__ int ba_curve(const float* __restrict__ c, int T, double sigma, int R,
   if (music) {
     double part = 0.0;
     for (int t = lo; t < hi; ++t) part += (double)sm[t];
-    mean = ba_sum(redd, part) / (double)T;
+    mean = m2d_block_sum<M2D_BA_THREADS>(part, redd) / (double)T;
   }
   int n = 0;
   for (int t = lo; t < hi; ++t) {
@@ -264,7 +253,7 @@ __device__ int ba_curve(const float* __restrict__ c, int T, double sigma, int R,
     if (out_mask) out_mask[t] = ev ? 1 : 0;
     n += ev ? 1 : 0;
   }
-  return (int)(ba_sum(redd, (double)n) + 0.5);
+  return (int)(m2d_block_sum<M2D_BA_THREADS>((double)n, redd) + 0.5);
 }
 
 // sum over the events t of Y of exp(-d(t)^2 / (2 sa^2)), d(t) the distance to the nearest event of X (X not empty)
@@ -299,7 +288,7 @@ __device__ double ba_nearest(const unsigned char* X, const unsigned char* Y, int
       sum += (double)expf(-(d * d) / den);
     }
   }
-  return ba_sum(redd, sum);
+  return m2d_block_sum<M2D_BA_THREADS>(sum, redd);
 }
 
 __global__ void __launch_bounds__(M2D_BA_THREADS) m2d_beat_align_kernel(

@@ -421,7 +421,7 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
 
 // ---------------------------------------------------------------------------------------------------------------------
 static bool tcn_enabled() {
-  static const bool on = [] { const char* e = getenv("M2D_TCN"); return !(e && e[0] == '0'); }();
+  static const bool on = m2d_env_on("M2D_TCN");
   return on;
 }
 
@@ -433,7 +433,7 @@ int m2d_tcn_conv_tile(int B, int Cin, int L, int Cout, int ks, int stride, int p
   if (Cin < 16 || Cin > 128 || L % 4 != 0 || B <= 0) return 0;
   const long long ntot = (long long)B * L;
   if (ntot * 128 >= (1LL << 29) || ntot >= (1 << 24)) return 0;   // 32-bit byte offsets, exact float division
-  static const int force = [] { const char* e = getenv("M2D_TCN_NT"); return e ? atoi(e) : 0; }();
+  static const int force = m2d_env_int("M2D_TCN_NT", 0);
   int best = 0;
   double best_cost = 0.0;
   const int cand[5] = {96, 64, 48, 32, 16};
@@ -476,7 +476,7 @@ static int tcn_conv_launch_ns(const M2dTcnConv& p, hipStream_t stream, const cha
 // from beyond the XCD's L2: 6 chunks of lead, not 2); M2D_TCN_NS=4: A/B lever
 template <int NT, int KS>
 static int tcn_conv_launch_nt(const M2dTcnConv& p, hipStream_t stream, const char* what) {
-  static const int ns = [] { const char* e = getenv("M2D_TCN_NS"); return e ? atoi(e) : 8; }();
+  static const int ns = m2d_env_int("M2D_TCN_NS", 8);
   if (ns == 4) return tcn_conv_launch_ns<NT, KS, 4>(p, stream, what);
   return tcn_conv_launch_ns<NT, KS, 8>(p, stream, what);
 }
@@ -833,7 +833,7 @@ __global__ void __launch_bounds__(256) m2d_tcn_wgrad_reduce_kernel(const float* 
 
 int m2d_tcn_wgrad_applicable(int B, int Cin, int L, int Cout, int ks, int stride, int pad) {
   if (!tcn_enabled()) return 0;
-  static const bool on = [] { const char* e = getenv("M2D_TCN_WGRAD"); return !(e && e[0] == '0'); }();
+  static const bool on = m2d_env_on("M2D_TCN_WGRAD");
   if (!on) return 0;
   if (Cout != 128 || stride != 1 || ks != 7 || pad != 3 || L % 60 != 0 || B <= 0) return 0;
   if (Cin < 16 || Cin > 4096) return 0;   // (any number of 32-channel groups; a ragged last group reads zeros)

@@ -10,12 +10,11 @@ critic's parameters are frozen instead of receiving gradients that the next zero
 throws away.
 """
 import contextlib
-import os
 
 import torch
 import torch.optim as optim
 
-from . import kernels, ops
+from . import kernels, levers, ops
 from .critic_step import CondCriticStep, CriticStep, GanCriticStep
 from .dp import GradExchange
 from .layers import DrawTape, Dropout, copy_stream, draw_tape, host_draw, to_device_async
@@ -84,7 +83,7 @@ class WganGpEngine:
         # torch.optim.Adam objects (param_groups, state_dict, schedulers) whose step is ONE multi-tensor HIP launch that
         # also rewrites the packed images of the conv weights it changes (optim.py; M2D_ADAM=torch: torch's own fused /
         # foreach implementation - the A/B lever; `fused_adam` then keeps its round-1 meaning)
-        if os.environ.get("M2D_ADAM", "m2d") == "torch":
+        if levers.value("M2D_ADAM", "m2d") == "torch":
             kw = {}
             if fused_adam is None:
                 fused_adam = dev.type == "cuda"
@@ -98,7 +97,7 @@ class WganGpEngine:
             self.optim_gen = M2dAdam(gen.parameters(), lr=lr_gen)
         # an optimizer step only invalidates the packed conv-weight images of ITS parameters (the generator's
         # stay valid through the critic iterations of a cycle)
-        self._keep_packs = os.environ.get("M2D_KEEP_PACKS", "1") != "0"
+        self._keep_packs = levers.on("M2D_KEEP_PACKS")
         self._critic_params = [p for p in critic.parameters() if p.dim() == 3] if self._keep_packs else None
         # (the generator's 2-D GRU weights too: their transposes are cached the same way)
         self._gen_params = [p for p in gen.parameters() if p.dim() in (2, 3)] if self._keep_packs else None
@@ -121,7 +120,7 @@ class WganGpEngine:
         self.last = {}
         self.last_full = {}  # most recent value of every scalar (generator scalars persist between G steps)
         # generator-forward pipelining (see _generator_forward_nograd)
-        self.pipeline_generator = os.environ.get("M2D_GEN_PIPELINE", "1") != "0"
+        self.pipeline_generator = levers.on("M2D_GEN_PIPELINE")
         self._inputs_ready = None
         self._gen_stream = None
         self._gen_params_ready = None
@@ -142,7 +141,7 @@ class WganGpEngine:
 
     def _manual_critic(self, step_cls, *args, **kw):
         """-> step_cls(critic, ...) (critic_step.py) if the critic qualifies and M2D_MANUAL_CRITIC is not 0, else None"""
-        if os.environ.get("M2D_MANUAL_CRITIC", "1") == "0" or not step_cls.supports(self.critic):
+        if not levers.on("M2D_MANUAL_CRITIC") or not step_cls.supports(self.critic):
             return None
         step = step_cls(self.critic, *args, **kw)
         if hasattr(step, "join_pairs"):
@@ -451,14 +450,14 @@ class Phase3Engine(WganGpEngine):
         self.gamma, self.beta, self.eta = float(cfg["gamma"]), float(cfg["beta"]), float(cfg["eta"])
         self.output_size = int(cfg.get("output_size", 69))
         self.ablated = bool(ablated)
-        self.early_pair_pass = os.environ.get("M2D_EARLY_PAIR", "1") != "0"
+        self.early_pair_pass = levers.on("M2D_EARLY_PAIR")
         # The loop body that holds a generator iteration runs the generator TWICE on one batch (phase3/train.py:195 for the
         # critic iteration, :222 for the generator iteration, fresh noise): encoder and audio GRU do not see the noise, so
         # the second pass's audio path equals the first's. With this on, the first pass of such a body keeps it (autograd
         # graph included) and the generator iteration runs only noise GRU + decoder on top, replaying the encoder's
         # BatchNorm running-statistics update with the same sums (SequenceGenerator.forward_keeping_audio_path).
         # M2D_REUSE_AUDIO_PATH=0: both passes in full, as the reference executes them.
-        self.reuse_audio_path = (os.environ.get("M2D_REUSE_AUDIO_PATH", "1") != "0"
+        self.reuse_audio_path = (levers.on("M2D_REUSE_AUDIO_PATH")
                                  and hasattr(gen, "forward_keeping_audio_path"))
         self.manual_critic = self._manual_critic(CriticStep, self.gamma, lp=False)
 

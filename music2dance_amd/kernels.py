@@ -10,12 +10,11 @@ the entry point's name; the weight images the GEMMs read are kept by `HipKernels
 """
 import contextlib
 import ctypes
-import os
 import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, levers
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 
@@ -69,7 +68,7 @@ def _bcl(x):
 
 
 _STREAM_SCRATCH = {}
-_FUSED_SPLITK = os.environ.get("M2D_FUSED_SPLITK", "1") != "0"
+_FUSED_SPLITK = levers.on("M2D_FUSED_SPLITK")
 _TICKET_WORDS = 16384   # 4 bytes per output tile of a split-K launch (include/m2d.h: 64 KB covers every shape)
 _BN_MAX_C = 4096        # widest channel / feature count a reducing call may have (the reference's widest: 1024)
 
@@ -136,7 +135,7 @@ _WS_BYTES = {}
 
 def _ws_bytes(name, *args):
     """Workspace size queries are pure functions of the shape: ask the library once per shape."""
-    if "M2D_PLAN" in os.environ:  # tuning builds: the plan (and its workspace) follows the environment
+    if levers.is_set("M2D_PLAN"):  # tuning builds: the plan (and its workspace) follows the environment
         return getattr(_lib.lib(), name)(*args)
     key = (name,) + args
     n = _WS_BYTES.get(key)
@@ -234,7 +233,7 @@ def set_plan_model(model):
     its c2 / c5 presets, the phase-2 train script does) - the engines do not touch it (round 5: an engine that switched it
     in its constructor changed the arithmetic of whatever ran next in the process). An explicit M2D_PLAN_MODEL in the
     environment wins. Cached workspace sizes follow the plans: dropped."""
-    if "M2D_PLAN_MODEL" in os.environ or not hasattr(_lib.lib(), "m2d_plan_model_set"):
+    if levers.is_set("M2D_PLAN_MODEL") or not hasattr(_lib.lib(), "m2d_plan_model_set"):
         return
     if _lib.lib().m2d_plan_model_get() != int(model):
         _lib.check(_lib.lib().m2d_plan_model_set(int(model)), "m2d_plan_model_set")
@@ -366,8 +365,8 @@ class HipKernels:
         return self._image(w, "T", lambda: w.t().contiguous())
 
     # ---------------------------------------------------------------- conv1d
-    _SEPARATE_BIAS = os.environ.get("M2D_SEPARATE_BIAS", "1") != "0"
-    _K4 = os.environ.get("M2D_K4", "1") != "0"  # A/B lever: 0 = stride-4 forwards through the generic engine
+    _SEPARATE_BIAS = levers.on("M2D_SEPARATE_BIAS")
+    _K4 = levers.on("M2D_K4")  # A/B lever: 0 = stride-4 forwards through the generic engine
     _K4_OK = {}
 
     def _k4(self, Cin, L, Cout, ks, stride, pad):

@@ -17,13 +17,12 @@ derivative needs an extra elementwise pass over HBM.
 Generator-only ops (BatchNorm, GRU, pooling, losses) are first-order.
 """
 import contextlib
-import os
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import kernels
+from . import kernels, levers
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 
@@ -94,8 +93,8 @@ def _c(t):
 # is the same at first and second order: gradients w.r.t. `x` get the in_act epilogue, gradients
 # w.r.t. `gy` / `h` get the act'(y) epilogue (that one is plain calculus: h = gy * act'(y)), and an
 # operand is read through a mask only when nobody pre-multiplied it.
-_FUSED_BIAS = os.environ.get("M2D_FUSED_BIAS", "1") != "0"  # dev switch for A/B timing
-_PREMASK = os.environ.get("M2D_PREMASK", "1") != "0"  # dev switch for A/B timing: 0 = masked operand loads
+_FUSED_BIAS = levers.on("M2D_FUSED_BIAS")  # dev switch for A/B timing
+_PREMASK = levers.on("M2D_PREMASK")  # dev switch for A/B timing: 0 = masked operand loads
 
 
 def _slope_of(act, slope):
@@ -697,12 +696,12 @@ GRU_SMALL_MAX = 16  # widest hidden size of m2d_gru_small_fwd / _bwd
 
 def _gru_small_enabled():
     """M2D_GRU_SMALL=0 sends every gru_final_state through gru_stack + a gather (A/B lever); read per call"""
-    return os.environ.get("M2D_GRU_SMALL", "1") != "0"
+    return levers.on("M2D_GRU_SMALL")
 
 
 def _gru_bwd_persist_enabled():
     """M2D_GRU_BWD_PERSIST=0: the stack's BPTT as step launches (tools/gru_bwd_probe.py flips it in-process); read per call"""
-    return os.environ.get("M2D_GRU_BWD_PERSIST", "1") != "0"
+    return levers.on("M2D_GRU_BWD_PERSIST")
 
 
 class _GRUFinal(Function):

@@ -11,12 +11,11 @@ iteration (losses.py:29, phase3/train.py:204-211), so inside that context its co
 computed once and shared (identical scores).
 """
 import contextlib
-import os
 
 import torch
 import torch.nn as nn
 
-from ... import kernels, ops
+from ... import kernels, levers, ops
 from ...layers import (GRU, BatchNorm1d, Conv1d, Linear, WindowView, batched_bn_counters, head_activation,
                        lengths_tensor, to_device_async)
 from ...utils import initialize_weights
@@ -29,11 +28,11 @@ def _descending(lengths):
     return ls
 
 
-_FUSED_BN_STATS = os.environ.get("M2D_FUSED_BN_STATS", "1") != "0"  # dev switch for A/B timing
+_FUSED_BN_STATS = levers.on("M2D_FUSED_BN_STATS")  # dev switch for A/B timing
 RELU_IN = (ops.ACT_RELU, 0.0)  # "my input is the sole-consumer output of a fused conv + ReLU" (ops.conv1d)
 
 
-_FUSED_BN_THEN = os.environ.get("M2D_FUSED_BN_THEN", "1") != "0"  # A/B lever: the U-Net's pool / upsample inside the BatchNorm pass
+_FUSED_BN_THEN = levers.on("M2D_FUSED_BN_THEN")  # A/B lever: the U-Net's pool / upsample inside the BatchNorm pass
 
 
 def _conv_bn(conv, bn, x, act, slope=0.0, into=None, then=None, then_out=None):
@@ -518,7 +517,7 @@ class SequenceDiscriminator(nn.Module):
     # leave most CUs idle between dependent kernels) runs on a side stream under the audio branch's
     # large convolutions. Autograd replays each node's backward on the stream of its forward, so
     # the first, second and final backward passes overlap the same way.
-    overlap_branches = os.environ.get("M2D_BRANCH_OVERLAP", "1") != "0"
+    overlap_branches = levers.on("M2D_BRANCH_OVERLAP")
 
     def _stick_code(self, x):
         dev = x.device
