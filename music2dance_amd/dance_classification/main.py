@@ -14,11 +14,9 @@ import os
 import torch
 
 from .. import runner
+from ..scoring import N_STYLES, STICK_CHANNELS
 from .archis.default import RecurrentDanceClassifier
 from .engine import ClassifierEngine
-
-N_STYLES = 4
-STICK_CHANNELS = 69
 
 
 def parse_args(argv=None):

@@ -19,7 +19,7 @@ real poses - every row of StickDataset(folder, normalize="minmax"), flattened to
         set's moments, and its sampling floor on the even / odd real rows;
     div_pose_real, div_pose_fake
         the mean pairwise distance of the standardised rows (at most DIVERSITY_ROWS rows of each set, a seeded subset:
-        the pairwise kernel is quadratic in fp64);
+        the pairwise kernel is quadratic in fp64); these five are scoring.distribution_scores';
     k, n_real, n_fake, checkpoint.
 
 The generator checkpoint defaults to the <logdir>/models/gen_<n>.pt with the largest n; with --synthetic and no
@@ -31,42 +31,34 @@ them into a ceil(sqrt(S))-column grid on the device, encodes it with visualize.e
 <logdir>/samples/sheet.jpg; every generated row goes to <logdir>/samples/poses.npy.
 """
 import argparse
-import glob
-import json
+import functools
 import math
 import os
-import re
 
 import numpy as np
 import torch
 
-from .. import metrics, runner, visualize
-from ..phase3.evaluate import json_safe
+from .. import metrics, runner, scoring, visualize
+from ..scoring import STICK_CHANNELS, json_safe, subset as _subset  # noqa: F401  (json_safe: the tests' name)
 from .archis.residual import Generator
 
-STICK_CHANNELS = 69
 DIVERSITY_ROWS = 4096
 SHEET_CELL = 300
 SPLIT_KEYS = ("precision", "recall", "density", "coverage")
-KEYS = (list(metrics.PRDC_KEYS) + ["%s_real_split" % s for s in SPLIT_KEYS]
-        + ["fd_pose", "fd_pose_real_split", "fd_pose_converged", "div_pose_real", "div_pose_fake", "k", "n_real", "n_fake",
-           "checkpoint"])
+POSE_KEYS = ("fd_pose", "fd_pose_real_split", "fd_pose_converged", "div_pose_real", "div_pose_fake")
+KEYS = (list(metrics.PRDC_KEYS) + ["%s_real_split" % s for s in SPLIT_KEYS] + list(POSE_KEYS)
+        + ["k", "n_real", "n_fake", "checkpoint"])
+latest_checkpoint = functools.partial(scoring.latest_checkpoint, stem="gen")
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("-c", "--config", type=str, required=True, help="phase-1 config file of the generator")
-    ap.add_argument("-l", "--logdir", type=str, required=True, help="run directory of the generator")
-    ap.add_argument("--gen-weights", type=str, default=None, help="generator state_dict (default: latest "
-                                                                    "<logdir>/models/gen_*.pt)")
+    scoring.add_common_flags(ap, 1, "gen", "uniform random real poses; random weights without a checkpoint")
     ap.add_argument("--samples", type=int, default=4096, help="poses to generate")
     ap.add_argument("--k", type=int, default=5, help="neighbours of the radii")
     ap.add_argument("--max-real", type=int, default=None, help="score against a seeded random subset of N real poses")
     ap.add_argument("--seed", type=int, default=0, help="seed of the noise and of the subsets")
     ap.add_argument("--sheet", type=int, default=25, help="poses on the contact sheet (0: none)")
-    ap.add_argument("--synthetic", action="store_true", help="uniform random real poses; random weights without a checkpoint")
-    ap.add_argument("--folder", type=str, default=None, help="dataset folder (overrides the YAML's `folder:`)")
-    ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
     opts = ap.parse_args(argv)
     if opts.k < 1:
         ap.error("--k needs K >= 1")
@@ -77,25 +69,6 @@ def parse_args(argv=None):
     if opts.sheet < 0:
         ap.error("--sheet must not be negative")
     return opts
-
-
-def latest_checkpoint(logdir):
-    """<logdir>/models/gen_<n>.pt with the largest n, or None"""
-    best, best_n = None, -1
-    for p in glob.glob(os.path.join(logdir, "models", "gen_*.pt")):
-        m = re.search(r"gen_(\d+)\.pt$", p)
-        if m and int(m.group(1)) > best_n:
-            best, best_n = p, int(m.group(1))
-    return best
-
-
-def _subset(rows, n, seed):
-    """a seeded random subset of n rows (all of them when there are no more), in their original order"""
-    if n is None or rows.shape[0] <= n:
-        return rows
-    g = torch.Generator().manual_seed(seed)
-    idx = torch.randperm(rows.shape[0], generator=g)[:n].sort().values
-    return rows[idx.to(rows.device)].contiguous()
 
 
 def real_rows(opts, cfg, device):
@@ -115,17 +88,8 @@ def scores(real, fake, k, seed=0):
     res = {key: float(val.cpu()) for key, val in metrics.prdc(real, fake, k).items()}
     split = metrics.prdc(real[0::2], real[1::2], k)
     res.update({"%s_real_split" % s: float(split[s].cpu()) for s in SPLIT_KEYS})
-    mean, cov = metrics.feature_moments(real)
-    Zr, Zf = metrics.standardize(real, mean, cov), metrics.standardize(fake, mean, cov)
-    pairs = [(Zr, Zf), (Zr[0::2], Zr[1::2])]
-    mom = [[metrics.feature_moments(x) for x in pair] for pair in pairs]
-    fd = metrics.frechet_from_moments(torch.stack([m[0][0] for m in mom]), torch.stack([m[0][1] for m in mom]),
-                                      torch.stack([m[1][0] for m in mom]), torch.stack([m[1][1] for m in mom]))
-    vals = fd["fd"].cpu().numpy()
-    res["fd_pose"], res["fd_pose_real_split"] = float(vals[0]), float(vals[1])
-    res["fd_pose_converged"] = bool((fd["converged"] != 0).all().cpu())
-    res["div_pose_real"] = float(metrics.mean_pairwise_distance(_subset(Zr, DIVERSITY_ROWS, seed))[0].cpu())
-    res["div_pose_fake"] = float(metrics.mean_pairwise_distance(_subset(Zf, DIVERSITY_ROWS, seed))[0].cpu())
+    dist = scoring.distribution_scores(real, fake, "pose", DIVERSITY_ROWS, seed)
+    res.update({key: dist[key] for key in POSE_KEYS})
     res.update(k=int(k), n_real=int(real.shape[0]), n_fake=int(fake.shape[0]))
     return res
 
@@ -155,12 +119,7 @@ def write_sheet(poses, path):
 @torch.no_grad()
 def evaluate(opts, cfg, device):
     gen = Generator(cfg["latent_vector_size"], cfg["size"], cfg["output_size"], cfg["nblocks_gen"]).to(device)
-    path = opts.gen_weights or latest_checkpoint(opts.logdir)
-    if path is not None:
-        gen.load_state_dict(torch.load(path, map_location=device))
-    elif not opts.synthetic:
-        raise SystemExit("no generator checkpoint: pass --gen-weights or train into %s/models" % opts.logdir)
-    gen.eval()
+    path = scoring.load_generator(gen, opts, "gen")
     real, scaler = real_rows(opts, cfg, device)
     if real.shape[0] < 2 * (opts.k + 1):
         raise SystemExit("%d real poses are too few for k = %d" % (real.shape[0], opts.k))
@@ -181,15 +140,7 @@ def evaluate(opts, cfg, device):
 
 
 def main(argv=None):
-    opts = parse_args(argv)
-    cfg = runner.load_config(opts.config)
-    device = runner.pick_device(opts.device)
-    os.makedirs(opts.logdir, exist_ok=True)
-    res = evaluate(opts, cfg, device)
-    with open(os.path.join(opts.logdir, "evaluation.json"), "w") as f:
-        json.dump(json_safe(res), f, indent=1, allow_nan=False)
-    print(json.dumps(json_safe(res), allow_nan=False))
-    return res
+    return scoring.run(parse_args, evaluate, argv, out="evaluation.json")       # no global seed: --seed is the seed
 
 
 if __name__ == "__main__":

@@ -11,10 +11,9 @@ import torch.nn as nn
 
 from ... import ops
 from ...layers import BatchNorm1d, Conv1d, Dropout, Linear, batched_bn_counters
+from ...scoring import N_STYLES as N_CLASSES
 from ...utils import initialize_weights
 from .default import LinearBlock, NoiseGen, TemporalBlock
-
-N_CLASSES = 4
 
 
 def _dropout(p):

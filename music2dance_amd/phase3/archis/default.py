@@ -434,6 +434,14 @@ class SequenceGenerator(nn.Module):
             return self.decoder(latent.reshape(-1, self.decoder.latent_size))
 
 
+def build_generator(cfg, device):
+    """the SequenceGenerator a phase-3 YAML describes"""
+    rate = cfg["dataset"]["audio_rate"]
+    return SequenceGenerator(int(cfg["window_size"] * rate), cfg["input_vector_size"], cfg["latent_vector_size"],
+                             cfg["size"], cfg["output_size"], cfg["noise_size"], cfg["nblocks_gen"], cfg["n_cells"],
+                             cfg["enc_type"], cfg["activ"], device)
+
+
 # --------------------------------------------------------------------------------------- critics
 class StickDiscriminator(nn.Module):
     """Pose branch: conv(k=init_ker)+ReLU, n_blocks TemporalBlocks, full-length conv -> code."""

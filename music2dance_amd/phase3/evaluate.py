@@ -15,7 +15,9 @@ The validation takes are <logdir>/trainvaltest_samples.json's `val_samples`, eac
 random crop per draw, as the reference's loader makes); all draws go through ONE eval-mode generator call (eval-mode
 BatchNorm keeps the rows independent, so only the order of the noise draws differs from the reference's batch-1 loop).
 The generator checkpoint defaults to the latest <logdir>/models/gpgen_*.pt. Writes <logdir>/evaluation.json, strict
-JSON: an undefined value (a confusion row without samples, the spread of a single sequence) is `null`.
+JSON: an undefined value (a confusion row without samples, the spread of a single sequence) is `null`. What this script
+shares with phase1.evaluate, phase2.evaluate and phase3.generate (flags, loaders, the take lookup, `confusion`,
+`jerk_stats`, `json_safe`, the Frechet / diversity block) is scoring.py's.
 
 --beat-align adds the music-dance beat alignment (metrics.beat_scores) of every real draw and of
 its generated counterpart against the draw's own audio row: `beat_align_{real,fake}_{mean,std}`,
@@ -37,33 +39,22 @@ same standardised kinetic features, real rows against generated rows: `precision
 `nn_real_to_real_median_kinetic` and `prdc_k`; `null` with fewer than K + 1 rows.
 """
 import argparse
-import glob
 import json
 import os
-import re
 
 import numpy as np
 import torch
 
-from .. import losses, ops, runner
-from ..dance_classification.archis.default import RecurrentDanceClassifier
-from .archis.default import SequenceGenerator
-
-N_STYLES = 4
-STICK_CHANNELS = 69
+from .. import metrics, ops, scoring
+from ..scoring import N_STYLES, STICK_CHANNELS, confusion, jerk_stats, json_safe, latest_checkpoint  # noqa: F401
+from .archis.default import build_generator
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("-c", "--config", type=str, required=True, help="phase-3 config file of the generator")
-    ap.add_argument("-l", "--logdir", type=str, required=True, help="run directory of the generator")
-    ap.add_argument("--gen-weights", type=str, default=None, help="generator state_dict (default: latest "
-                                                                    "<logdir>/models/gpgen_*.pt)")
+    scoring.add_common_flags(ap, 3, "gpgen", "random poses / audio / styles of the dataset's shapes")
     ap.add_argument("--classifier", type=str, required=True, help="RecurrentDanceClassifier state_dict")
     ap.add_argument("--repeats", type=int, default=20, help="draws of every validation take")
-    ap.add_argument("--synthetic", action="store_true", help="random poses / audio / styles of the dataset's shapes")
-    ap.add_argument("--folder", type=str, default=None, help="dataset folder (overrides the YAML's `folder:`)")
-    ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
     ap.add_argument("--beat-align", action="store_true", help="also score the beat alignment of the real and the "
                                                               "generated dances with their music")
     ap.add_argument("--frechet", action="store_true", help="also score the Frechet distance and the diversity of the "
@@ -85,35 +76,6 @@ def parse_args(argv=None):
     return opts
 
 
-def latest_checkpoint(logdir):
-    """<logdir>/models/gpgen_<iteration>.pt with the largest iteration, or None"""
-    best, best_it = None, -1
-    for p in glob.glob(os.path.join(logdir, "models", "gpgen_*.pt")):
-        m = re.search(r"gpgen_(\d+)\.pt$", p)
-        if m and int(m.group(1)) > best_it:
-            best, best_it = p, int(m.group(1))
-    return best
-
-
-def confusion(real_pred, fake_pred, n_classes=N_STYLES):
-    """-> (row-normalised C x C matrix of real-predicted (row) vs fake-predicted (column) labels, NaN rows where a
-    real label never occurs; the raw counts)."""
-    real_pred = np.asarray(real_pred, dtype=np.int64).reshape(-1)
-    fake_pred = np.asarray(fake_pred, dtype=np.int64).reshape(-1)
-    counts = np.zeros((n_classes, n_classes), dtype=np.int64)
-    np.add.at(counts, (real_pred, fake_pred), 1)
-    rows = counts.sum(axis=1, keepdims=True).astype(np.float64)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        cm = np.where(rows > 0, counts / np.where(rows > 0, rows, 1.0), np.nan)
-    return cm, counts
-
-
-def jerk_stats(values):
-    """(mean, unbiased standard deviation) of per-sequence jerkiness values (torch.std's default; NaN for one value)"""
-    v = np.asarray(values, dtype=np.float64).reshape(-1)
-    return float(v.mean()), (float(v.std(ddof=1)) if v.size > 1 else float("nan"))
-
-
 def beat_stats(align, cover, tag):
     """The beat-alignment keys of one side (`tag` = real / fake): mean and unbiased standard deviation of beat_align
     and beat_cover over the rows where the score is defined (both are NaN together), and how many rows those are"""
@@ -131,7 +93,6 @@ def beat_rows(audio, real_i, fake_i, hop, rate):
     """-> {'real': (align, cover), 'fake': (align, cover)}, numpy (N,) each: metrics.beat_scores of the inverse-scaled
     dances (N, T, 69) against the audio rows (N, S) they were drawn with. A drawn take's audio row starts at its first
     pose frame (SequenceDataset.sample_batch), so pose frame t belongs to samples [t hop, (t + 1) hop) of the row."""
-    from .. import metrics
     out = {}
     for tag, poses in (("real", real_i), ("fake", fake_i)):
         s = metrics.beat_scores(audio, poses.contiguous(), hop, rate=rate)
@@ -142,16 +103,17 @@ def beat_rows(audio, real_i, fake_i, hop, rate):
 def kinetic_rows(real_i, fakes_i, fps, up_axis=1, prdc_k=None):
     """The keys of --frechet (and, for more than one generated set, of --modes): real_i (N, T, 69) and the list fakes_i
     of generated sets of the same shape, inverse-scaled; set k row n is the k-th dance made for the music of real row
-    n. Features are standardised by the real set's moments; both Frechet pairs go through ONE m2d_frechet call. The
-    only host reads are the final scalars. prdc_k (--prdc): also metrics.prdc of the standardised real rows against
-    the first generated set with that many neighbours, keys suffixed `_kinetic`, and `prdc_k`."""
-    from .. import metrics
+    n. The Frechet and diversity keys are scoring.distribution_scores' of the kinetic features. prdc_k (--prdc): also
+    metrics.prdc of the standardised real rows against the first generated set with that many neighbours, keys
+    suffixed `_kinetic`, and `prdc_k`. The only host reads are the final scalars."""
     nan = float("nan")
     N = real_i.shape[0]
     Fr = metrics.kinetic_features(real_i.contiguous(), fps, up_axis)
     Ff = [metrics.kinetic_features(f.contiguous(), fps, up_axis) for f in fakes_i]
-    res = {"fd_kinetic": nan, "fd_kinetic_real_split": nan, "div_kinetic_real": nan, "div_kinetic_fake": nan,
-           "fd_kinetic_converged": None, "kinetic_dims": int(Fr.shape[1])}
+    dist = scoring.distribution_scores(Fr, Ff, "kinetic")
+    res = {key: dist[key] for key in ("fd_kinetic", "fd_kinetic_real_split", "div_kinetic_real", "div_kinetic_fake",
+                                      "fd_kinetic_converged")}
+    res["kinetic_dims"] = int(Fr.shape[1])
     if len(fakes_i) > 1:
         res["multimodality_kinetic"] = nan
     if prdc_k is not None:
@@ -159,20 +121,7 @@ def kinetic_rows(real_i, fakes_i, fps, up_axis=1, prdc_k=None):
         res["prdc_k"] = int(prdc_k)
     if N < 2:
         return res
-    mean, cov = metrics.feature_moments(Fr)
-    Zr = metrics.standardize(Fr, mean, cov)
-    Zf = [metrics.standardize(f, mean, cov) for f in Ff]
-    pairs = [(Zr, Zf[0])] + ([(Zr[0::2], Zr[1::2])] if N >= 4 else [])
-    mom = [[metrics.feature_moments(x) for x in pair] for pair in pairs]
-    fd = metrics.frechet_from_moments(torch.stack([m[0][0] for m in mom]), torch.stack([m[0][1] for m in mom]),
-                                      torch.stack([m[1][0] for m in mom]), torch.stack([m[1][1] for m in mom]))
-    vals = fd["fd"].cpu().numpy()
-    res["fd_kinetic"] = float(vals[0])
-    if len(pairs) > 1:
-        res["fd_kinetic_real_split"] = float(vals[1])
-    res["fd_kinetic_converged"] = bool((fd["converged"] != 0).all().cpu())
-    res["div_kinetic_real"] = float(metrics.mean_pairwise_distance(Zr)[0].cpu())
-    res["div_kinetic_fake"] = float(metrics.mean_pairwise_distance(Zf[0])[0].cpu())
+    Zr, Zf = dist["Zr"], dist["Zf"]
     if len(Zf) > 1:
         Z = torch.stack(Zf, 1).reshape(N * len(Zf), -1).contiguous()       # the dances of a slice are consecutive rows
         res["multimodality_kinetic"] = float(metrics.mean_pairwise_distance(Z, groups=N).mean().cpu())
@@ -200,24 +149,6 @@ def summary(real_jerk, fake_jerk, real_pred, fake_pred, n_classes=N_STYLES, beat
     return res
 
 
-def json_safe(v):
-    """NaN / inf -> None (JSON null), recursively through lists and dicts"""
-    if isinstance(v, dict):
-        return {k: json_safe(x) for k, x in v.items()}
-    if isinstance(v, (list, tuple)):
-        return [json_safe(x) for x in v]
-    if isinstance(v, float) and not np.isfinite(v):
-        return None
-    return v
-
-
-def build_generator(cfg, device):
-    rate = cfg["dataset"]["audio_rate"]
-    return SequenceGenerator(int(cfg["window_size"] * rate), cfg["input_vector_size"], cfg["latent_vector_size"],
-                             cfg["size"], cfg["output_size"], cfg["noise_size"], cfg["nblocks_gen"], cfg["n_cells"],
-                             cfg["enc_type"], cfg["activ"], device)
-
-
 def _takes(opts, cfg, device):
     """-> (real poses (N, T, 69), audio tracks (N, S), labels (N,), scaler, window, hop): the validation takes,
     each drawn `repeats` times."""
@@ -240,36 +171,21 @@ def _takes(opts, cfg, device):
         labels = torch.randint(0, N_STYLES, (n_val,), generator=g, device=device).repeat(opts.repeats)
         scaler = D.MinMaxScaler().fit(real.reshape(-1, STICK_CHANNELS).cpu().numpy())
         return real, audio, labels, scaler, window, hop
-    with open(split) as f:
-        val_dirs = json.load(f)["val_samples"]
-    folder = runner.dataset_folder(cfg, opts.folder)
-    sticks = D.StickDataset(folder, normalize="minmax")
-    dataset = D.SequenceDataset(folder, ds, dance_types=cfg["dance_types"], scaler=sticks.scaler, withaudio=True)
+    _, idx, dataset, scaler = scoring.validation_takes(opts, cfg)
     dataset.truncate()
-    where = {d: i for i, d in enumerate(dataset.dirs)}
-    missing = [d for d in val_dirs if d not in where]
-    if missing:
-        raise SystemExit("validation takes not in the dataset: %s" % missing[:5])
-    idx = [where[d] for d in val_dirs]
     parts = [dataset.sample_batch(idx, device) for _ in range(opts.repeats)]
     real = torch.cat([p[0].reshape(len(idx), dataset.stick_length, STICK_CHANNELS) for p in parts]).float()
     audio = torch.cat([p[2] for p in parts]).float()
     labels = torch.cat([p[3].reshape(-1) for p in parts]).long()
-    return real, audio, labels, sticks.scaler, int(cfg["window_size"] * dataset.aud_rate), dataset.ratio
+    return real, audio, labels, scaler, int(cfg["window_size"] * dataset.aud_rate), dataset.ratio
 
 
 @torch.no_grad()
 def evaluate(opts, cfg, device):
     from ..utils import slice_audio_batch
     gen = build_generator(cfg, device)
-    path = opts.gen_weights or latest_checkpoint(opts.logdir)
-    if path is not None:
-        gen.load_state_dict(torch.load(path, map_location=device))
-    elif not opts.synthetic:
-        raise SystemExit("no generator checkpoint: pass --gen-weights or train into %s/models" % opts.logdir)
-    classifier = RecurrentDanceClassifier(STICK_CHANNELS, 128, N_STYLES).to(device)
-    classifier.load_state_dict(torch.load(opts.classifier, map_location=device))
-    gen.eval(), classifier.eval()
+    scoring.load_generator(gen, opts)
+    classifier = scoring.load_classifier(opts.classifier, device)
 
     real, audio, labels, scaler, window, hop = _takes(opts, cfg, device)
     N, T, _ = real.shape
@@ -280,8 +196,8 @@ def evaluate(opts, cfg, device):
     # jerkiness per sequence on the inverse-scaled poses (phase3/test.py:76-104)
     real_i = scaler.inverse_transform_device(real)
     fake_i = scaler.inverse_transform_device(fake.contiguous())
-    real_jerk = torch.stack([losses.jerkiness(real_i[i:i + 1].permute(0, 2, 1)) for i in range(N)])
-    fake_jerk = torch.stack([losses.jerkiness(fake_i[i:i + 1].permute(0, 2, 1)) for i in range(N)])
+    real_jerk = torch.stack(scoring.jerk_per_sequence(real_i))
+    fake_jerk = torch.stack(scoring.jerk_per_sequence(fake_i))
 
     # style classification of every real take and its generated counterpart (phase3/test.py:107-140)
     _, real_pred = ops.cross_entropy_pred(classifier(real.permute(0, 2, 1).contiguous()), labels)
@@ -302,16 +218,7 @@ def evaluate(opts, cfg, device):
 
 
 def main(argv=None):
-    opts = parse_args(argv)
-    cfg = runner.load_config(opts.config)
-    device = runner.pick_device(opts.device)
-    os.makedirs(opts.logdir, exist_ok=True)
-    torch.manual_seed(0)
-    res = evaluate(opts, cfg, device)
-    with open(os.path.join(opts.logdir, "evaluation.json"), "w") as f:
-        json.dump(json_safe(res), f, indent=1, allow_nan=False)
-    print(json.dumps(json_safe(res), allow_nan=False))
-    return res
+    return scoring.run(parse_args, evaluate, argv, out="evaluation.json", seed=0)
 
 
 if __name__ == "__main__":

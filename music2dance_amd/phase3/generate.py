@@ -33,6 +33,8 @@ generation.json records `resampler` and, per track that comes from an --audio fi
 alignment (metrics.beat_scores) of the saved poses with the track at the model's rate - with
 --resampler poly the device's own conversion of the file (the streamed pieces, concatenated, equal it bit for bit).
 Tracks longer than the alignment kernel's row limit fail loudly.
+
+The common flags, the checkpoint loading and the --val lookup are scoring.py's.
 """
 import argparse
 import json
@@ -43,9 +45,10 @@ import numpy as np
 import torch
 
 from .. import audio as A
-from .. import kernels, runner
+from .. import kernels, runner, scoring
+from ..scoring import STICK_CHANNELS, json_safe
 from ..utils import slice_audio_batch
-from .evaluate import STICK_CHANNELS, build_generator, json_safe, latest_checkpoint
+from .archis.default import build_generator
 
 DEFAULT_HOP = 640  # 16 kHz audio, 25 fps video
 
@@ -159,20 +162,13 @@ def generate_track(gen, audio, seed, hop=DEFAULT_HOP, pad=None):
 # --------------------------------------------------------------------------------------- command line
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("-c", "--config", type=str, required=True, help="phase-3 config file of the generator")
-    ap.add_argument("-l", "--logdir", type=str, required=True, help="run directory of the generator")
-    ap.add_argument("--gen-weights", type=str, default=None, help="generator state_dict (default: latest "
-                                                                    "<logdir>/models/gpgen_*.pt)")
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--audio", type=str, nargs="+", help="wav files to dance to")
     src.add_argument("--val", action="store_true", help="the takes listed under val_samples in "
                                                         "<logdir>/trainvaltest_samples.json")
-    src.add_argument("--synthetic", action="store_true", help="a random 600-frame track (random weights without a "
-                                                              "checkpoint)")
+    scoring.add_common_flags(ap, 3, "gpgen", "a random 600-frame track (random weights without a checkpoint)", src)
     ap.add_argument("--chunk-frames", type=int, default=25, help="frames of audio per push (0: one call per track)")
     ap.add_argument("--seed", type=int, default=0, help="noise seed")
-    ap.add_argument("--folder", type=str, default=None, help="dataset folder (overrides the YAML's `folder:`)")
-    ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
     ap.add_argument("--video", action="store_true", help="also render each saved dance to <logdir>/samples/<name>.avi "
                                                          "(300 x 300 stick figures at the config's video_rate)")
     ap.add_argument("--encoder", choices=("pil", "hip"), default=None,
@@ -215,10 +211,9 @@ def _tracks(opts, cfg):
         T = 600
         audio = 0.1 * torch.randn(T * int(ds["audio_rate"] // ds["video_rate"]), generator=g)
         return [("synthetic", audio.numpy(), ds["audio_rate"], None)], scaler
-    folder = runner.dataset_folder(cfg, opts.folder)
-    scaler = D.StickDataset(folder, normalize="minmax").scaler
     if opts.audio:
         from scipy.io import wavfile
+        scaler = D.StickDataset(runner.dataset_folder(cfg, opts.folder), normalize="minmax").scaler
         poly = getattr(opts, "resampler", "fft") == "poly"
         out = []
         for p in opts.audio:
@@ -230,16 +225,9 @@ def _tracks(opts, cfg):
                 out.append((name, load_track(p, ds["audio_rate"]), ds["audio_rate"],
                             int(wavfile.read(p, mmap=True)[0])))
         return out, scaler
-    split = os.path.join(opts.logdir, "trainvaltest_samples.json")
-    with open(split) as f:
-        val_dirs = json.load(f)["val_samples"]
-    dataset = D.SequenceDataset(folder, ds, dance_types=cfg["dance_types"], scaler=scaler, withaudio=True)
-    where = {d: i for i, d in enumerate(dataset.dirs)}
-    missing = [d for d in val_dirs if d not in where]
-    if missing:
-        raise SystemExit("validation takes not in the dataset: %s" % missing[:5])
-    return [(os.path.basename(os.path.normpath(d)), np.asarray(dataset.musics[where[d]], dtype=np.float32),
-             ds["audio_rate"], None) for d in val_dirs], scaler
+    val_dirs, idx, dataset, scaler = scoring.validation_takes(opts, cfg)
+    return [(os.path.basename(os.path.normpath(d)), np.asarray(dataset.musics[i], dtype=np.float32),
+             ds["audio_rate"], None) for d, i in zip(val_dirs, idx)], scaler
 
 
 def _pctl(v, q):
@@ -315,14 +303,7 @@ def generate(opts, cfg, device):
     rate = int(ds["audio_rate"])
     hop = int(ds["audio_rate"] // ds["video_rate"])
     gen = build_generator(cfg, device)
-    path = opts.gen_weights or latest_checkpoint(opts.logdir)
-    if path is not None:
-        if not os.path.exists(path):
-            raise SystemExit("generator checkpoint %s not found" % path)
-        gen.load_state_dict(torch.load(path, map_location=device))
-    elif not opts.synthetic:
-        raise SystemExit("no generator checkpoint: pass --gen-weights or train into %s/models" % opts.logdir)
-    gen.eval()
+    path = scoring.load_generator(gen, opts)
     window = gen.window_size
     pad = window - hop
     tracks, scaler = _tracks(opts, cfg)
@@ -370,14 +351,7 @@ def generate(opts, cfg, device):
 
 
 def main(argv=None):
-    opts = parse_args(argv)
-    cfg = runner.load_config(opts.config)
-    device = runner.pick_device(opts.device)
-    os.makedirs(opts.logdir, exist_ok=True)
-    torch.manual_seed(0)
-    res = generate(opts, cfg, device)
-    print(json.dumps(json_safe(res), allow_nan=False))
-    return res
+    return scoring.run(parse_args, generate, argv, seed=0)       # generate wrote samples/generation.json itself
 
 
 if __name__ == "__main__":

@@ -243,7 +243,7 @@ def test_generate_with_the_polyphase_resampler(tmp_path):
     from music2dance_amd import runner
     from music2dance_amd.data import StickDataset, write_synthetic_dataset
     from music2dance_amd.phase3 import generate as G
-    from music2dance_amd.phase3.evaluate import build_generator
+    from music2dance_amd.phase3.archis.default import build_generator
     cfg_path = os.path.join(ROOT, "music2dance_amd", "phase3", "configs", "default.yaml")
     cfg = runner.load_config(cfg_path)
     data = write_synthetic_dataset(str(tmp_path / "data"), n_takes=4, seconds=2)

@@ -85,7 +85,7 @@ def main():
     from scipy.io import wavfile
     from music2dance_amd.data import write_synthetic_dataset
     from music2dance_amd.phase3 import generate as G
-    from music2dance_amd.phase3.evaluate import build_generator
+    from music2dance_amd.phase3.archis.default import build_generator
     cfg_path = os.path.join(ROOT, "music2dance_amd", "phase3", "configs", "default.yaml")
     with tempfile.TemporaryDirectory() as tmp:
         wav = os.path.join(tmp, "song.wav")
