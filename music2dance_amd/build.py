@@ -46,6 +46,7 @@ def build(force=False, verbose=True, stamp=True):
     os.makedirs(obj_dir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    headers.append(os.path.join(os.path.dirname(PKG_DIR), "include", "m2d.h"))   # m2d_common.h includes the public header
     jobs = []
     objs = []
     for src in SOURCES:

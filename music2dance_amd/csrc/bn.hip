@@ -12,6 +12,7 @@
 // fused. Partial sums are combined in fp64 so the result does not depend on the grid.
 #include "m2d_common.h"
 
+// (not m2d_divmod of m2d_device.h on purpose: with the branch-free form these kernels compile to different code, unmeasured)
 __device__ __forceinline__ void bn_divmod(int n, int d, float inv, int& q, int& r) {
   q = (int)((float)n * inv);
   r = n - q * d;

@@ -10,6 +10,7 @@
 // double backward needs (losses.py:40-44): every optional `*_mask` argument multiplies
 // an operand / the result by (mask > 0 ? 1 : slope), i.e. by the derivative of the fused
 // ReLU / LeakyReLU, so the first- and second-order chains need no extra HBM pass.
+#include "conv1d_thin.h"
 #include "gemm_engine.h"
 #include "tcn.h"
 
@@ -19,29 +20,6 @@ static inline int conv_out_len(int L, int ks, int stride, int pad) {
 }
 
 static inline bool fits_i32(long long v) { return v >= 0 && v < 2147483647LL; }
-
-// conv1d_thin.hip: vector-ALU kernels for Cin = 1, k = 25, stride 4 (HBM-bound layers)
-// Window view of a padded track (B, S): the logical input is (B*T, 1, window), window t of track b
-// starting at b*S + t*hop (utils.slice_audio_batch of the reference, never materialised). T == 0: dense.
-struct M2dWinView {
-  int T, S, hop;
-};
-bool m2d_thin_applicable(int Cin, int Cout, int ks, int stride);
-bool m2d_thin_long_applicable(int Cin, int Cout, int ks, int stride, int pad, int L);
-size_t m2d_thin_long_stats_ws(int B, int Lout);
-int m2d_thin_long_fwd(const float* x, const float* w, const float* bias, float* y, int B, int L, int ks, int stride, int pad,
-                      int Lout, int act, float slope, const M2dWinView* wv, double* stats, void* ws, size_t ws_bytes,
-                      hipStream_t stream);
-size_t m2d_thin_bwd_weight_ws(int B, int Cout, int ks, int Lout);
-size_t m2d_thin_fwd_stats_ws(int B, int Lout);
-int m2d_thin_fwd(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cout, int ks,
-                 int stride, int pad, int Lout, int act, float slope, const float* out_mask, float out_mask_slope,
-                 const M2dWinView* wv, double* stats, void* ws, size_t ws_bytes, hipStream_t stream);
-int m2d_thin_bwd_data(const float* dy, const float* w, float* dx, int B, int L, int Cout, int ks, int stride,
-                      int pad, int Lout, const float* dy_mask, float dy_mask_slope, hipStream_t stream);
-int m2d_thin_bwd_weight(const float* x, const float* dy, float* dw, float* dbias, int B, int L, int Cout, int ks,
-                        int stride, int pad, int Lout, const float* dy_mask, float dy_mask_slope, void* ws,
-                        size_t ws_bytes, const M2dWinView* wv, hipStream_t stream);
 
 // Forward conv as a GEMM. Cin >= 16: K ordered (tap, channel) - hi = tap, lo = ci - over the
 // packed weights wp (Cout, ks, Cin): every 16-chunk sits on one tap, so the padding window is

@@ -9,7 +9,9 @@
 //   backward-data  : Z[tap][position] = W^T dy (K = channels), then the overlap-add of the taps
 //   backward-weight: C[tap][channel], K = positions (deterministic two-stage sum of per-block slabs, no atomics)
 // Masks (activation derivative) follow the convention of gemm_engine.h: value *= (mask > 0 ? 1 : slope).
-#include "m2d_common.h"
+#include "conv1d_thin.h"
+#include "gemm_engine.h"   // m2d_rowsums_reduce
+#include "m2d_device.h"
 
 #define THIN_MAX_K 32
 
@@ -35,13 +37,11 @@ struct ThinArgs {
 // 64-position tiles: the (32 co x 64 l) slice of dy (times the activation mask) goes through a
 // wave-private LDS image with coalesced 16-B loads, the x windows are read straight from
 // global memory (lanes 0-31 read 32 consecutive samples). HBM-bound: dy (+ mask) is read once.
-typedef float thin_f32x16 __attribute__((ext_vector_type(16)));
-typedef float thin_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned thin_u32x4 __attribute__((ext_vector_type(4)));
 
 // m2d_act_sel (m2d_common.h) behind plain tests of the launch-uniform `act`, with `act` a constant in each arm: the compiler
 // then moves the tests out of the unrolled epilogue. The forward kernel sits just under its 128-VGPR ceiling, and the
 // branch-free form with a run-time `act` spills 8 registers there.
+// (A separate form on purpose: do not fold it into m2d_act / m2d_act_sel.)
 __device__ __forceinline__ float thin_act(float v, int act, float slope) {
   if (act == 0) return v;
   if (act == 1) return m2d_act_sel(v, 1, 0.f);
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(256) thin_bwd_weight_mfma_kernel(const ThinArg
   const float* mkn = (MASKED && a.mask) ? a.mask + (size_t)n * 32 * a.Lout : nullptr;
   float* tl = smem[wave];
   float* xw = tl + 32 * LD;
-  thin_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const int i31 = lane & 31, h = lane >> 5;
@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(256) thin_bwd_data_mfma_kernel(const ThinArgs 
   };
   // Z tile of 32 positions starting at image column c0: D[row = kk][col = position]
   auto zmma = [&](int c0) {
-    thin_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -294,7 +294,7 @@ __global__ void __launch_bounds__(256) thin_bwd_data_mfma_kernel(const ThinArgs 
     fetch(dv[0], qa - 64);  // the 64-wide fetch ending at qa; columns 32..63 are the ones multiplied
     land(dv[0]);
     sync();
-    const thin_f32x16 z = zmma(32);
+    const f32x16 z = zmma(32);
     sync();
 #pragma unroll
     for (int r = 0; r < 16; ++r)
@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(256) thin_bwd_data_mfma_kernel(const ThinArgs 
       for (int i = 0; i < 8; ++i) dv[0][i] = dv[1][i];
     }
     if (l0 + 64 * DEPTH < qb) fetch(dv[DEPTH - 1], l0 + 64 * DEPTH);
-    const thin_f32x16 z0 = zmma(0), z1 = zmma(32);
+    const f32x16 z0 = zmma(0), z1 = zmma(32);
     sync();
     // Z image: rows 0..HALO-1 from the carry, rows HALO.. = this tile's 64 positions
 #pragma unroll
@@ -468,16 +468,16 @@ thin_fwd_mfma_kernel(const ThinArgs a, int tiles_per_row, int total_tiles) {
     const int n = tile / tiles_per_row;
     const int p0 = (tile - n * tiles_per_row) * 32;
     const float* xr = a.xT > 0 ? a.x + (size_t)(n / a.xT) * a.xS + (size_t)(n % a.xT) * a.xhop : a.x + (size_t)n * a.L;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)xr, (short)0, (int)((unsigned)a.L * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = m2d_rsrc(xr, (unsigned)a.L * 4u);
     const int l = p0 + c31;
     // (positions past the row's end: l >= Lout -> force out of range; their products are never stored)
-    const unsigned voff = l < a.Lout ? (unsigned)((l * S - a.pad + h) * 4) : 0x80000000u;
+    const unsigned voff = l < a.Lout ? (unsigned)((l * S - a.pad + h) * 4) : M2D_OOB;
 #pragma unroll
     for (int ks = 0; ks < NS; ++ks) {
 #ifdef THIN_X_NOGATHER   // experiment (wrong results): no x gathers
       dst[ks] = (float)((voff + ks) & 7);
 #else
-      dst[ks] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)voff + 8 * ks, 0, 0));
+      dst[ks] = m2d_bload(rx, voff + (unsigned)(8 * ks));
 #endif
     }
     if (LAST_DEAD && h == 1) dst[NS - 1] = 0.f;
@@ -486,18 +486,17 @@ thin_fwd_mfma_kernel(const ThinArgs a, int tiles_per_row, int total_tiles) {
     const int n = tile / tiles_per_row;
     const int p0 = (tile - n * tiles_per_row) * 32;
     const bool interior = valign == 4 && p0 + 32 <= a.Lout;   // (uniform)
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * 32 * a.Lout), (short)0, (int)sample_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc((void*)((a.mask ? a.mask : a.out) + (size_t)n * 32 * a.Lout), (short)0,
-                                                                        (int)(a.mask ? sample_bytes : 0u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro = m2d_rsrc(a.out + (size_t)n * 32 * a.Lout, sample_bytes);
+    const __amdgpu_buffer_rsrc_t rm = m2d_rsrc((a.mask ? a.mask : a.out) + (size_t)n * 32 * a.Lout, a.mask ? sample_bytes : 0u);
     const unsigned eo = (unsigned)crow * row_bytes + (unsigned)(p0 + 4 * cq) * 4u;   // channel row crow + 8 i: + 8 i row_bytes
     // this tile's mask rows, fetched before the MFMAs (interior tiles; the other path reads them in place)
-    thin_f32x4 mk[4];
+    m2d_f32x4 mk[4];
     if (interior && a.mask) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        mk[i] = __builtin_bit_cast(thin_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rm, (int)(eo + (unsigned)(8 * i) * row_bytes), 0, 0));
+        mk[i] = m2d_bload16(rm, eo + (unsigned)(8 * i) * row_bytes);
     }
-    thin_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -511,8 +510,8 @@ thin_fwd_mfma_kernel(const ThinArgs a, int tiles_per_row, int total_tiles) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int co = crow + 8 * i;
-        const thin_f32x4 q = *reinterpret_cast<const thin_f32x4*>(im + co * LDP + 4 * cq);
-        thin_f32x4 v;
+        const m2d_f32x4 q = *reinterpret_cast<const m2d_f32x4*>(im + co * LDP + 4 * cq);
+        m2d_f32x4 v;
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = thin_act(q[j] + bv[i], a.act, a.slope);
         if (a.mask) {
@@ -522,7 +521,7 @@ thin_fwd_mfma_kernel(const ThinArgs a, int tiles_per_row, int total_tiles) {
 #ifdef THIN_X_NOSTORE    // experiment (wrong results): no output stores
         if (v[0] == 12345.678f)
 #endif
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(thin_u32x4, v), ro, (int)(eo + (unsigned)(8 * i) * row_bytes), 0, 0);
+        m2d_bstore16(v, ro, eo + (unsigned)(8 * i) * row_bytes);
         // statistics: summed per lane over ALL the wave's tiles; the 8 lanes of a channel row meet once, at the end
         st1[i] += (v[0] + v[1]) + (v[2] + v[3]);
         st2[i] += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
@@ -627,12 +626,6 @@ thin_fwd_mfma_kernel(const ThinArgs a, int tiles_per_row, int total_tiles) {
   flush_stats();
 }
 
-struct M2dWinView {
-  int T, S, hop;
-};
-
-int m2d_rowsums_reduce(const float* part, int P, int M, double* sums, double* scratch, hipStream_t stream);  // gemm_engine.hip
-
 // per-tile partials + the scratch of the two-stage row sum (256 groups x 32 rows x fp64 pair)
 static int thin_fwd_tiles_per_row(int Lout) { return m2d_ceil_div(Lout, 32); }
 // statistics partials: one (sum, sum of squares) pair per channel and WAVE of the grid (at most 256 x 16 workgroups x 4)
@@ -717,27 +710,27 @@ __global__ void __launch_bounds__(512) thin_long_fwd_kernel(const ThinArgs a, in
   const unsigned row_bytes = (unsigned)a.Lout * 4u;
   const unsigned sample_bytes = 32u * row_bytes;
 
-  thin_f32x4 seg[NP];
+  m2d_f32x4 seg[NP];
   auto fetch = [&](int tile) {
     const int n = tile / tiles_per_row;
     const int p0 = (tile - n * tiles_per_row) * 32;
     const float* xr = a.xT > 0 ? a.x + (size_t)(n / a.xT) * a.xS + (size_t)(n % a.xT) * a.xhop : a.x + (size_t)n * a.L;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)xr, (short)0, (int)((unsigned)a.L * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = m2d_rsrc(xr, (unsigned)a.L * 4u);
     // piece q of the segment = samples p0 S - pad4 + 4 q ..+3, pad4 = pad rounded up to 4 (S, L multiples of 4: a piece
     // is inside the window or outside it)
     const int first = p0 * S - a.pad - lead;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int q = lane + 64 * i;
-      const unsigned voff = q < SEG4 ? (unsigned)((first + 4 * q) * 4) : 0x80000000u;
-      seg[i] = __builtin_bit_cast(thin_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)voff, 0, 0));
+      const unsigned voff = q < SEG4 ? (unsigned)((first + 4 * q) * 4) : M2D_OOB;
+      seg[i] = m2d_bload16(rx, voff);
     }
   };
   auto land = [&]() {
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int q = lane + 64 * i;
-      if (q < SEG4) *reinterpret_cast<thin_f32x4*>(xs + 4 * q) = seg[i];
+      if (q < SEG4) *reinterpret_cast<m2d_f32x4*>(xs + 4 * q) = seg[i];
     }
   };
   int tile = __builtin_amdgcn_readfirstlane(blockIdx.x * 8 + wave);
@@ -777,7 +770,7 @@ __global__ void __launch_bounds__(512) thin_long_fwd_kernel(const ThinArgs a, in
   for (;;) {
     const int next = tile + nwaves;
     if (next < total_tiles) fetch(next);
-    thin_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -791,16 +784,18 @@ __global__ void __launch_bounds__(512) thin_long_fwd_kernel(const ThinArgs a, in
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // (the segment's reads are done: the next one may land while the epilogue runs)
     if (next < total_tiles) land();
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * 32 * a.Lout), (short)0, (int)sample_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro = m2d_rsrc(a.out + (size_t)n * 32 * a.Lout, sample_bytes);
     const unsigned eo = (unsigned)crow * row_bytes + (unsigned)(p0 + 4 * cq) * 4u;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int co = crow + 8 * i;
-      const thin_f32x4 q = *reinterpret_cast<const thin_f32x4*>(im + co * LDP + 4 * cq);
-      thin_f32x4 v;
+      const m2d_f32x4 q = *reinterpret_cast<const m2d_f32x4*>(im + co * LDP + 4 * cq);
+      m2d_f32x4 v;
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = thin_act(q[j] + bv[i], a.act, a.slope);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(thin_u32x4, v), ro, (int)(eo + (unsigned)(8 * i) * row_bytes), 0, 0);
+      // (the builtin itself, not m2d_bstore16: through the helper this kernel's store addresses are scheduled differently -
+      // unmeasured, so the code stays as it was)
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(m2d_u32x4, v), ro, (int)(eo + (unsigned)(8 * i) * row_bytes), 0, 0);
       // statistics: a lane's four values of channel row crow + 8 i, summed over ALL the wave's tiles in registers; the
       // eight lanes of a row meet once, after the last tile (one partial per (wave, channel): the tile -> wave assignment
       // is fixed, so the sums are repeatable)

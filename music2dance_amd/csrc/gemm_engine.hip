@@ -1,10 +1,9 @@
 // Implementation of the separable-gather fp32-MFMA GEMM engine (see gemm_engine.h).
 #include "gemm_engine.h"
+#include "m2d_device.h"
 #include <atomic>
 #include <map>
 #include <mutex>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Wave layout of a BM x BN block tile: NW waves as WM x WN, each owning TM x TN accumulator tiles of 32 x 32.
 // NW = 4 (256 threads) everywhere except the LDS-direct 128 x 128 kernel, which also runs with NW = 8 (512 threads, a
@@ -19,15 +18,6 @@ struct M2dTiling {
   static constexpr int TN = BN / (32 * WN);
   static constexpr int NTH = 64 * NW;
 };
-
-// n / d and n % d for 0 <= n < 2^24 (exact in fp32; the launcher rejects larger extents). Branch-free.
-__device__ __forceinline__ void m2d_divmod(int n, int d, float inv, int& q, int& r) {
-  q = (int)((float)n * inv);
-  r = n - q * d;
-  const int adj = (r < 0 ? -1 : 0) + (r >= d ? 1 : 0);
-  q += adj;
-  r -= adj * d;
-}
 
 // Workgroup -> tile map (p.tile_map). The hardware deals consecutive workgroup ids round-robin over the 8 XCDs, each
 // with an L2 of its own, so with tile = workgroup id (N fastest) the tiles resident on one XCD are ~96 different N
@@ -56,28 +46,8 @@ __device__ __forceinline__ void m2d_tile_of(int tile_map, int& bx, int& by) {
   bx = nn;
 }
 
-// Staging loads are raw buffer loads: an element that is padding, past a lo tail or past the
-// last row gets the byte offset M2D_OOB, which the hardware range check (num_records =
-// operand extent < 2^31) turns into 0.0f whatever scalar offset is added. No select on the
-// data, no divergent branch, nothing that forces a wait on the load before the LDS store.
-#define M2D_OOB 0x80000000u
-#define M2D_BAD 0x40000000
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t m2d_rsrc(const float* p, unsigned nbytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)nbytes, 0x00020000);
-}
-
-// voff: per-lane byte offset (range-checked), soff: wave-uniform byte offset (SGPR)
-__device__ __forceinline__ float m2d_bload(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, soff, 0));
-}
-
-// the same load with the LDS as its destination: lane L of the wave writes dst[L] (M0 = dst, wave-uniform);
-// lanes whose offset fails the range check write 0.0f (measured on gfx950), so padding needs no separate store
-typedef __attribute__((address_space(3))) float m2d_lds_f;
-__device__ __forceinline__ void m2d_bload_lds(__amdgpu_buffer_rsrc_t r, float* dst, unsigned voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (m2d_lds_f*)dst, 4, (int)voff, soff, 0, 0);
-}
+// Staging loads are raw buffer loads (m2d_device.h): an element that is padding, past a lo tail or past the last row
+// gets the byte offset M2D_OOB and reads as 0.0f.
 
 // element offset of row-side index hi (two-level for window views, see M2dOperand)
 __device__ __forceinline__ int m2d_hi_offset(const M2dOperand& op, int hi) {
@@ -233,12 +203,12 @@ struct TileMap {
     if constexpr (UNIFORM) {
       const unsigned voff = ((unsigned)(posr + P) < lim_eff) ? full : M2D_OOB;
 #pragma unroll
-      for (int i = 0; i < NE; ++i) m2d_bload_lds(rs, dst + (KS * i) * LD, voff, i * ls4);
+      for (int i = 0; i < NE; ++i) m2d_bload_lds<4>(rs, dst + (KS * i) * LD, voff, i * ls4);
     } else {
 #pragma unroll
       for (int i = 0; i < NE; ++i) {
         const int pp = (lo0 + kb + KS * i < kdiv) ? P + (KS * i) * op.k_pos_lo : M2D_BAD;
-        m2d_bload_lds(rs, dst + (KS * i) * LD, ((unsigned)(posr + pp) < lim_eff) ? full + (unsigned)(i * ls4) : M2D_OOB, 0);
+        m2d_bload_lds<4>(rs, dst + (KS * i) * LD, ((unsigned)(posr + pp) < lim_eff) ? full + (unsigned)(i * ls4) : M2D_OOB, 0);
       }
     }
   }
@@ -429,18 +399,12 @@ __device__ __forceinline__ void m2d_acc_init(const M2dGemmParams& p, const M2dOu
 __device__ __forceinline__ float4 m2d_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void m2d_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
-typedef unsigned int m2d_u32x4 __attribute__((__vector_size__(16)));
-typedef float m2d_vf32x4 __attribute__((__vector_size__(16)));
-__device__ __forceinline__ void m2d_bstore1(__amdgpu_buffer_rsrc_t r, unsigned voff, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, 0, 0);
-}
+// the 16-byte buffer accesses of m2d_device.h on HIP's float4
 __device__ __forceinline__ void m2d_bstore4(__amdgpu_buffer_rsrc_t r, unsigned voff, float4 v) {
-  m2d_vf32x4 w;
-  w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(m2d_u32x4, w), r, (int)voff, 0, 0);
+  m2d_bstore16(m2d_f32x4{v.x, v.y, v.z, v.w}, r, voff);
 }
 __device__ __forceinline__ float4 m2d_bload4(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  const m2d_vf32x4 w = __builtin_bit_cast(m2d_vf32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
+  const m2d_f32x4 w = m2d_bload16(r, voff);
   return make_float4(w[0], w[1], w[2], w[3]);
 }
 
@@ -618,7 +582,7 @@ __device__ __forceinline__ void m2d_tile_epilogue(const M2dGemmParams& p, const 
               } else {
                 float x = img[it * (RS * 32)];
                 x = m2d_act_sel(x, act, O.slope) * (((keep >> it) & 1u) ? 1.f : ms);
-                m2d_bstore1(rso, voff, x);
+                m2d_bstore1(x, rso, voff);
               }
             }
           }
@@ -725,10 +689,10 @@ __device__ __forceinline__ void m2d_tile_epilogue(const M2dGemmParams& p, const 
             x *= ((keep >> qq) & 1u) ? 1.f : ms;
             if (has_res && !O.mask_last) {
               const float sum = x + m2d_bload(M2D_RS(O.residual), voff, 0);
-              if (two_out) m2d_bstore1(M2D_RS(O.sum_out), voff, sum);
+              if (two_out) m2d_bstore1(sum, M2D_RS(O.sum_out), voff);
               else x = sum;
             }
-            m2d_bstore1(M2D_RS(out_base), voff, x);
+            m2d_bstore1(x, M2D_RS(out_base), voff);
             if (stats) {  // the 32 lanes (columns) that share this row; one partial per (row, 32-column tile)
               a1 = ok ? x : 0.f;
               a2 = ok ? x * x : 0.f;
@@ -770,7 +734,7 @@ __device__ __forceinline__ bool m2d_splitk_fixup(const M2dGemmParams& p, int spl
   // push the LDS-direct kernels from five to four workgroups per CU)
   const unsigned tile = blockIdx.y * gridDim.x + blockIdx.x;
   const unsigned slab_bytes = gridDim.x * gridDim.y * (unsigned)p.splits * TILE_BYTES;  // < 2^31: launcher-checked
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.slab, (short)0, (int)slab_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = m2d_rsrc(p.slab, slab_bytes);
   const unsigned mine = (tile * (unsigned)p.splits + (unsigned)split) * TILE_BYTES + (unsigned)tid * 16u;
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -778,10 +742,9 @@ __device__ __forceinline__ bool m2d_splitk_fixup(const M2dGemmParams& p, int spl
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) {
-        m2d_vf32x4 v;
+        m2d_f32x4 v;
         v[0] = acc[i][j][4 * r4]; v[1] = acc[i][j][4 * r4 + 1]; v[2] = acc[i][j][4 * r4 + 2]; v[3] = acc[i][j][4 * r4 + 3];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(m2d_u32x4, v), rs,
-                                               (int)(mine + (unsigned)(((i * TN + j) * 4 + r4) * PLANE)), 0, 16 /* sc1 */);
+        m2d_bstore16<M2D_SC1>(v, rs, mine + (unsigned)(((i * TN + j) * 4 + r4) * PLANE));
       }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -801,12 +764,9 @@ __device__ __forceinline__ bool m2d_splitk_fixup(const M2dGemmParams& p, int spl
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
       for (int s = 0; s < p.splits; ++s) {
         const unsigned from = (tile * (unsigned)p.splits + (unsigned)s) * TILE_BYTES + (unsigned)tid * 16u;
-        m2d_vf32x4 f[4];
+        m2d_f32x4 f[4];
 #pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4)
-          // (whole-vector bit cast: an element-wise cast of this builtin's result is narrowed to one dword load)
-          f[r4] = __builtin_bit_cast(m2d_vf32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                      rs, (int)(from + (unsigned)(((i * TN + j) * 4 + r4) * PLANE)), 0, 16 /* sc1 */));
+        for (int r4 = 0; r4 < 4; ++r4) f[r4] = m2d_bload16<M2D_SC1>(rs, from + (unsigned)(((i * TN + j) * 4 + r4) * PLANE));
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
           acc[i][j][4 * r4] += f[r4][0]; acc[i][j][4 * r4 + 1] += f[r4][1];
@@ -1376,12 +1336,8 @@ __global__ void __launch_bounds__(256, 2) m2d_gemm_dl_tall_kernel(const M2dGemmP
   M2D_STAMP_AT(3);
 }
 
-// LDS byte address of a pointer into a __shared__ array, and a 16-byte LDS read the compiler does not see as a memory
-// access (see m2d_conv_k4_kernel)
-typedef float m2d_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned m2d_lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const float*)p;
-}
+// a 16-byte LDS read the compiler does not see as a memory access (see m2d_conv_k4_kernel; part of that kernel's
+// schedule, so it lives here and not in m2d_device.h)
 __device__ __forceinline__ m2d_f32x4 m2d_ds_read_b128(unsigned addr) {
   m2d_f32x4 v;
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
@@ -1547,13 +1503,13 @@ __global__ void __launch_bounds__(256, 5) m2d_conv_k4_kernel(const M2dGemmParams
       float* db = st + 16 * BM + (wave * BN) * 4;
 #pragma unroll
       for (int h = 0; h < HA; ++h)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (m2d_lds_f*)(da + h * 256), 16, (int)(kok ? va[h] : M2D_OOB), sa, 0, 0);
+        m2d_bload_lds<16>(ra, da + h * 256, kok ? va[h] : M2D_OOB, sa);
 #pragma unroll
       for (int h = 0; h < HB; ++h) {
         // (the group's offset is added on the vector side: the hardware range check sees the vector offset only, and
         // a row's own offset is negative for the first positions of the first sample - "x - P" in front of the tensor)
         const bool ok = kok && (unsigned)(posb[h] + 4 * g) < (unsigned)B.lim;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (m2d_lds_f*)(db + h * 256), 16, (int)(ok ? vb[h] + (unsigned)sb : M2D_OOB), 0, 0, 0);
+        m2d_bload_lds<16>(rb, db + h * 256, ok ? vb[h] + (unsigned)sb : M2D_OOB, 0);
       }
       kg += 4;
       cs += 1;

@@ -12,9 +12,8 @@
 // The step is latency-bound (<= 22 MFLOP), not roofline-bound; the grid is sized to put
 // every (row-group, unit-slice) on its own CU.
 #include "m2d_common.h"
+#include "m2d_device.h"
 #include <mutex>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define GRU_UNROLL 16
 
@@ -41,9 +40,9 @@ __global__ void __launch_bounds__(256) m2d_gru_fwd_step_kernel(const GruFwdArgs 
   const int u0 = blockIdx.x * 16;
   const int b0 = blockIdx.y * 16;
   const int H = a.H, T = a.T, t = a.t;
-  f32x4 acc[3];
+  m2d_f32x4 acc[3];
 #pragma unroll
-  for (int g = 0; g < 3; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int g = 0; g < 3; ++g) acc[g] = (m2d_f32x4){0.f, 0.f, 0.f, 0.f};
 
   if (t > 0) {
     const int arow = b0 + (lane & 15);
@@ -129,7 +128,7 @@ __global__ void __launch_bounds__(256) m2d_gru_bwd_step_kernel(const GruBwdArgs 
   const int u0 = blockIdx.x * 16;
   const int b0 = blockIdx.y * 16;
   const int H = a.H, T = a.T, t = a.t;
-  f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+  m2d_f32x4 acc = (m2d_f32x4){0.f, 0.f, 0.f, 0.f};
   const bool has_next = (t + 1) < T;
   if (has_next) {
     const int arow = b0 + (lane & 15);
@@ -276,7 +275,7 @@ __device__ __forceinline__ void gru_put_state(const GruStackFwdArgs& a, int l, i
 
 template <int NB, int NW>
 __device__ __forceinline__ void gru_mac(const float* arow, bool rok, const float* wt, int H, int ncol, int bcol,
-                                        bool cok, int wave, int lane, f32x4 (&acc)[NB], const int (&col_of)[NB]) {
+                                        bool cok, int wave, int lane, m2d_f32x4 (&acc)[NB], const int (&col_of)[NB]) {
   // acc[j] += A[16 rows, K = H] * W^T[:, col_of[j] * H + bcol]; this wave takes k-steps wave, wave+NW, ...
   const int nsteps = (H + 3) / 4;
   for (int s0 = wave; s0 < nsteps; s0 += NW * GRU_UNROLL) {
@@ -314,9 +313,9 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_stack_fwd_kernel(cons
   const int u0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
   const int H = a.H, T = a.T;
   // accumulators: 0 = r (input + hidden), 1 = z (input + hidden), 2 = gh_n, 3 = gi_n
-  f32x4 acc[4];
+  m2d_f32x4 acc[4];
 #pragma unroll
-  for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int g = 0; g < 4; ++g) acc[g] = (m2d_f32x4){0.f, 0.f, 0.f, 0.f};
   const int arow = b0 + (lane & 15);
   const int bcol = u0 + (lane & 15);
   const bool rok = arow < a.B, cok = bcol < H;
@@ -394,13 +393,13 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_stack_fwd_kernel(cons
     }
   } else {
     if (use_i) {
-      f32x4 i3[3] = {acc[0], acc[1], acc[3]};
+      m2d_f32x4 i3[3] = {acc[0], acc[1], acc[3]};
       const int cols[3] = {0, 1, 2};
       gru_mac<3, NW>(a.out[l - 1] + ((size_t)arow * T + t) * H, rok, a.w_ih_t[l], H, 3 * H, bcol, cok, wave, lane, i3, cols);
       acc[0] = i3[0]; acc[1] = i3[1]; acc[3] = i3[2];
     }
     if (use_h) {
-      f32x4 h3[3] = {acc[0], acc[1], acc[2]};
+      m2d_f32x4 h3[3] = {acc[0], acc[1], acc[2]};
       const int cols[3] = {0, 1, 2};
       gru_mac<3, NW>(hsrc, rok, a.w_hh_t[l], H, 3 * H, bcol, cok, wave, lane, h3, cols);
       acc[0] = h3[0]; acc[1] = h3[1]; acc[2] = h3[2];
@@ -478,8 +477,6 @@ struct GruPersistArgs {
 
 typedef __attribute__((address_space(1))) unsigned gru_gu32;
 typedef __attribute__((address_space(1))) float gru_gf32;
-typedef unsigned int gru_u32x4 __attribute__((__vector_size__(16)));
-typedef float gru_f32x4 __attribute__((__vector_size__(16)));
 
 __device__ __forceinline__ float gru_ld_sc1(const float* p) {
   return __hip_atomic_load((gru_gf32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -518,10 +515,11 @@ __device__ __forceinline__ bool gru_load_rows(__amdgpu_buffer_rsrc_t rs, const f
     const int k0 = 16 * j + 4 * q;
     if (j < nblk && rok) {
       if (vec && k0 + 3 < H) {
-        // (whole-vector bit cast: see gru_bwd_contract)
-        const gru_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((row_off + k0) << 2), 0, 16 /* sc1 */);
+        // (the builtin itself, not m2d_bload16<M2D_SC1>: through the helper the sentinel tests below compile to a
+        // different order of scalar ORs in both persistent forward kernels - unmeasured, so the code stays as it was)
+        const m2d_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((row_off + k0) << 2), 0, M2D_SC1);
         bad = bad || v[0] == GRU_SENTINEL || v[1] == GRU_SENTINEL || v[2] == GRU_SENTINEL || v[3] == GRU_SENTINEL;
-        const gru_f32x4 f = __builtin_bit_cast(gru_f32x4, v);
+        const m2d_f32x4 f = __builtin_bit_cast(m2d_f32x4, v);
         av[i][0] = f[0]; av[i][1] = f[1]; av[i][2] = f[2]; av[i][3] = f[3];
       } else {
 #pragma unroll
@@ -609,8 +607,8 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(co
     }
   }
   const unsigned obytes = (unsigned)((size_t)a.B * T * H * sizeof(float));  // < 2^31: checked by the launcher
-  const __amdgpu_buffer_rsrc_t own_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.out[l], (short)0, (int)obytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t low_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.out[use_i ? l - 1 : l], (short)0, (int)obytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t own_rs = m2d_rsrc(a.out[l], obytes);
+  const __amdgpu_buffer_rsrc_t low_rs = m2d_rsrc(a.out[use_i ? l - 1 : l], obytes);
   const int row = (tid & 255) >> 4, col = tid & 15;
   const int b = b0 + row, u = u0 + col;
   const bool owner = tid < 256 && b < a.B && u < H;
@@ -633,9 +631,9 @@ __global__ void __launch_bounds__(64 * GRU_FWD_NW) m2d_gru_persist_fwd_kernel(co
   }
   for (int t = 0; t < T; ++t) {
     const bool use_h = t > 0 || h0 != nullptr;
-    f32x4 acc[4];
+    m2d_f32x4 acc[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int g = 0; g < 4; ++g) acc[g] = (m2d_f32x4){0.f, 0.f, 0.f, 0.f};
     float gir = nir, giz = niz, gin = nin;
     if (owner && l == 0 && t + 1 < T) {
       const float* gi = a.gi0 + ((size_t)b * T + t + 1) * 3 * H;
@@ -747,7 +745,7 @@ struct GruStackBwdArgs {
 // persistent kernel below uses the same assignment and order (bit-identical sums).
 template <int NW>
 __device__ __forceinline__ void gru_mac1(const float* arow, bool rok, const float* w, int K, int H, int bcol, bool cok,
-                                         int wave, int lane, f32x4& acc) {
+                                         int wave, int lane, m2d_f32x4& acc) {
   const int nblk = (K + 15) / 16;
   const int q = lane >> 4;
   const bool vec = (K & 3) == 0;
@@ -778,7 +776,7 @@ __global__ void __launch_bounds__(64 * GRU_BWD_NW) m2d_gru_stack_bwd_kernel(cons
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int u0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
   const int H = a.H, T = a.T;
-  f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+  m2d_f32x4 acc = (m2d_f32x4){0.f, 0.f, 0.f, 0.f};
   const int arow = b0 + (lane & 15);
   const int bcol = u0 + (lane & 15);
   const bool rok = arow < a.B, cok = bcol < H;
@@ -841,7 +839,7 @@ struct GruPersistBwdArgs {
 template <int NW>
 __device__ __forceinline__ void gru_bwd_contract(const float* base, size_t row_off, bool rok,
                                                  const float (&bw)[GRU_BWD_MAXB][4], int K, int wave, int lane, bool vec,
-                                                 __amdgpu_buffer_rsrc_t rs, f32x4& acc) {
+                                                 __amdgpu_buffer_rsrc_t rs, m2d_f32x4& acc) {
   const int nblk = (K + 15) / 16;
   const int q = lane >> 4;
   float av[GRU_BWD_MAXB][4];
@@ -850,12 +848,9 @@ __device__ __forceinline__ void gru_bwd_contract(const float* base, size_t row_o
     const int j = wave + NW * i;
     const int k0 = 16 * j + 4 * q;
     if (j < nblk && vec && k0 + 3 < K) {
-      // (rows past the batch read through offset 0x80000000: the descriptor's range check returns zeros)
-      const unsigned off = rok ? (unsigned)((row_off + k0) << 2) : 0x80000000u;
-      // (whole-vector bit cast: element-wise __builtin_bit_cast(float, v[i]) on the builtin's result is narrowed to
-      // ONE dword load by hipcc 7.2 - every element then reads as the first)
-      const gru_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 16 /* sc1 */);
-      const gru_f32x4 f = __builtin_bit_cast(gru_f32x4, v);
+      // (rows past the batch: the descriptor's range check returns zeros)
+      const unsigned off = rok ? (unsigned)((row_off + k0) << 2) : M2D_OOB;
+      const m2d_f32x4 f = m2d_bload16<M2D_SC1>(rs, off);
       av[i][0] = f[0]; av[i][1] = f[1]; av[i][2] = f[2]; av[i][3] = f[3];
     } else {
 #pragma unroll
@@ -879,9 +874,8 @@ __global__ void __launch_bounds__(64 * GRU_BWD_NW) m2d_gru_persist_bwd_kernel(co
   const int H = a.H, T = a.T, K = 3 * a.H;
   const bool vec = (K & 3) == 0;
   const unsigned gbytes = (unsigned)((size_t)a.B * T * K * sizeof(float));  // < 2^31: checked by the launcher
-  const __amdgpu_buffer_rsrc_t gh_rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.dgh[blockIdx.z], (short)0, (int)gbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t gi_rs = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.dgi[(int)blockIdx.z + 1 < a.L ? blockIdx.z + 1 : blockIdx.z], (short)0, (int)gbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t gh_rs = m2d_rsrc(a.dgh[blockIdx.z], gbytes);
+  const __amdgpu_buffer_rsrc_t gi_rs = m2d_rsrc(a.dgi[(int)blockIdx.z + 1 < a.L ? blockIdx.z + 1 : blockIdx.z], gbytes);
   float (*red)[256] = reinterpret_cast<float (*)[256]>(lds);
   __shared__ int go;
   const int l = blockIdx.z, bt = blockIdx.y;
@@ -920,7 +914,7 @@ __global__ void __launch_bounds__(64 * GRU_BWD_NW) m2d_gru_persist_bwd_kernel(co
 
   for (int t = T - 1; t >= 0; --t) {
     const bool has_next = (t + 1) < T;
-    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    m2d_f32x4 acc = (m2d_f32x4){0.f, 0.f, 0.f, 0.f};
     // values written before the launch: fetched under the waits
     float r = 0.f, z = 0.f, n = 0.f, hn = 0.f, hprev = 0.f, znext = 0.f, dtop = 0.f;
     if (owner) {
@@ -1248,17 +1242,7 @@ int m2d_gru_stack_bwd(const float* dout, const float* const* out, const float* c
 // around memory, so the waits stay where they are written.
 #define GRU_SMALL_MAX 16
 #define GRU_SMALL_CH 8
-#define GRU_OOB 0x80000000u
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gru_rsrc(const float* p, size_t nbytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, p ? (int)nbytes : 0, 0x00020000);
-}
-__device__ __forceinline__ float gru_bload(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, 0));
-}
-__device__ __forceinline__ void gru_bstore(float v, __amdgpu_buffer_rsrc_t r, unsigned voff) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, 0, 0);
-}
 // s_waitcnt vmcnt(0) (expcnt / lgkmcnt left alone): the one wait of a chunk
 __device__ __forceinline__ void gru_wait_vm() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
@@ -1289,23 +1273,25 @@ __global__ void __launch_bounds__(64) m2d_gru_small_fwd_kernel(const float* __re
   if (row && lengths) len = min(max(lengths[b], 0), T);
   // resources cover this wave's rows only; offsets are bytes from the wave's first row
   const size_t BTH = (size_t)B * T * H, rowT = (size_t)rows * T;
-  const __amdgpu_buffer_rsrc_t rg = gru_rsrc(gi + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
-  const __amdgpu_buffer_rsrc_t ro = gru_rsrc(out ? out + (size_t)b0 * T * H : nullptr, rowT * H * 4);
+  // a NULL tensor gets a zero-sized resource (the test is applied to every tensor, optional or not)
+  auto rsrc = [](const float* p, size_t nbytes) { return m2d_rsrc(p, p ? (unsigned)nbytes : 0u); };
+  const __amdgpu_buffer_rsrc_t rg = rsrc(gi + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
+  const __amdgpu_buffer_rsrc_t ro = rsrc(out ? out + (size_t)b0 * T * H : nullptr, rowT * H * 4);
   __amdgpu_buffer_rsrc_t rs[4];
 #pragma unroll
-  for (int p = 0; p < 4; ++p) rs[p] = gru_rsrc(saved ? saved + p * BTH + (size_t)b0 * T * H : nullptr, rowT * H * 4);
+  for (int p = 0; p < 4; ++p) rs[p] = rsrc(saved ? saved + p * BTH + (size_t)b0 * T * H : nullptr, rowT * H * 4);
   const unsigned gbase = 4u * ((unsigned)grp * T * 3 * H + j), obase = 4u * ((unsigned)grp * T * H + j);
-  auto goff = [&](int t) { return (act && t >= 0 && t < T) ? gbase + 4u * (unsigned)(t * 3 * H) : GRU_OOB; };
-  auto ooff = [&](int t) { return (act && t >= 0 && t < T) ? obase + 4u * (unsigned)(t * H) : GRU_OOB; };
+  auto goff = [&](int t) { return (act && t >= 0 && t < T) ? gbase + 4u * (unsigned)(t * 3 * H) : M2D_OOB; };
+  auto ooff = [&](int t) { return (act && t >= 0 && t < T) ? obase + 4u * (unsigned)(t * H) : M2D_OOB; };
 
   float cg[GRU_SMALL_CH][3], ng[GRU_SMALL_CH][3];  // gi of this chunk / of the next one
   float po[5][GRU_SMALL_CH];                        // h, r, z, n, W_hn h + b_hn of the previous chunk
 #pragma unroll
   for (int s = 0; s < GRU_SMALL_CH; ++s) {
     const unsigned o = goff(s);
-    cg[s][0] = gru_bload(rg, o);
-    cg[s][1] = gru_bload(rg, o + 4u * H);
-    cg[s][2] = gru_bload(rg, o + 8u * H);
+    cg[s][0] = m2d_bload(rg, o);
+    cg[s][1] = m2d_bload(rg, o + 4u * H);
+    cg[s][2] = m2d_bload(rg, o + 8u * H);
 #pragma unroll
     for (int q = 0; q < 5; ++q) po[q][s] = 0.f;
   }
@@ -1316,16 +1302,16 @@ __global__ void __launch_bounds__(64) m2d_gru_small_fwd_kernel(const float* __re
 #pragma unroll
     for (int s = 0; s < GRU_SMALL_CH; ++s) {
       const unsigned o = ooff(c0 - GRU_SMALL_CH + s);
-      gru_bstore(po[0][s], ro, o);
+      m2d_bstore1(po[0][s], ro, o);
 #pragma unroll
-      for (int p = 0; p < 4; ++p) gru_bstore(po[1 + p][s], rs[p], o);
+      for (int p = 0; p < 4; ++p) m2d_bstore1(po[1 + p][s], rs[p], o);
     }
 #pragma unroll
     for (int s = 0; s < GRU_SMALL_CH; ++s) {
       const unsigned o = goff(c0 + GRU_SMALL_CH + s);
-      ng[s][0] = gru_bload(rg, o);
-      ng[s][1] = gru_bload(rg, o + 4u * H);
-      ng[s][2] = gru_bload(rg, o + 8u * H);
+      ng[s][0] = m2d_bload(rg, o);
+      ng[s][1] = m2d_bload(rg, o + 4u * H);
+      ng[s][2] = m2d_bload(rg, o + 8u * H);
     }
 #pragma unroll
     for (int s = 0; s < GRU_SMALL_CH; ++s) {
@@ -1358,9 +1344,9 @@ __global__ void __launch_bounds__(64) m2d_gru_small_fwd_kernel(const float* __re
 #pragma unroll
   for (int s = 0; s < GRU_SMALL_CH; ++s) {
     const unsigned o = ooff(clast + s);
-    gru_bstore(po[0][s], ro, o);
+    m2d_bstore1(po[0][s], ro, o);
 #pragma unroll
-    for (int p = 0; p < 4; ++p) gru_bstore(po[1 + p][s], rs[p], o);
+    for (int p = 0; p < 4; ++p) m2d_bstore1(po[1 + p][s], rs[p], o);
   }
   if (act) h_n[(size_t)b * H + j] = hlast;
 }
@@ -1397,16 +1383,18 @@ __global__ void __launch_bounds__(64) m2d_gru_small_bwd_kernel(const float* __re
   if (row && lengths) len = min(max(lengths[b], 0), T);
   const float dhn = (act && dh_n) ? dh_n[(size_t)b * H + j] : 0.f;
   const size_t BTH = (size_t)B * T * H, rowT = (size_t)rows * T;
+  // a NULL tensor gets a zero-sized resource (the test is applied to every tensor, optional or not)
+  auto rsrc = [](const float* p, size_t nbytes) { return m2d_rsrc(p, p ? (unsigned)nbytes : 0u); };
   __amdgpu_buffer_rsrc_t rs[4];
 #pragma unroll
-  for (int p = 0; p < 4; ++p) rs[p] = gru_rsrc(saved + p * BTH + (size_t)b0 * T * H, rowT * H * 4);
-  const __amdgpu_buffer_rsrc_t rout = gru_rsrc(out + (size_t)b0 * T * H, rowT * H * 4);
-  const __amdgpu_buffer_rsrc_t rd = gru_rsrc(dout ? dout + (size_t)b0 * T * H : nullptr, rowT * H * 4);
-  const __amdgpu_buffer_rsrc_t rgi = gru_rsrc(dgi + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
-  const __amdgpu_buffer_rsrc_t rgh = gru_rsrc(dgh + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
+  for (int p = 0; p < 4; ++p) rs[p] = rsrc(saved + p * BTH + (size_t)b0 * T * H, rowT * H * 4);
+  const __amdgpu_buffer_rsrc_t rout = rsrc(out + (size_t)b0 * T * H, rowT * H * 4);
+  const __amdgpu_buffer_rsrc_t rd = rsrc(dout ? dout + (size_t)b0 * T * H : nullptr, rowT * H * 4);
+  const __amdgpu_buffer_rsrc_t rgi = rsrc(dgi + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
+  const __amdgpu_buffer_rsrc_t rgh = rsrc(dgh + (size_t)b0 * T * 3 * H, rowT * 3 * H * 4);
   const unsigned obase = 4u * ((unsigned)grp * T * H + j), gbase = 4u * ((unsigned)grp * T * 3 * H + j);
-  auto ooff = [&](int t) { return (act && t >= 0 && t < T) ? obase + 4u * (unsigned)(t * H) : GRU_OOB; };
-  auto goff = [&](int t) { return (act && t >= 0 && t < T) ? gbase + 4u * (unsigned)(t * 3 * H) : GRU_OOB; };
+  auto ooff = [&](int t) { return (act && t >= 0 && t < T) ? obase + 4u * (unsigned)(t * H) : M2D_OOB; };
+  auto goff = [&](int t) { return (act && t >= 0 && t < T) ? gbase + 4u * (unsigned)(t * 3 * H) : M2D_OOB; };
 
   // operands of one step: r, z, n, W_hn h + b_hn, h_{t-1}, dout
   float cur[6][GRU_SMALL_CH], nxt[6][GRU_SMALL_CH];
@@ -1417,9 +1405,9 @@ __global__ void __launch_bounds__(64) m2d_gru_small_bwd_kernel(const float* __re
       const int t = t0 - s;
       const unsigned o = ooff(t);
 #pragma unroll
-      for (int p = 0; p < 4; ++p) v[p][s] = gru_bload(rs[p], o);
-      v[4][s] = gru_bload(rout, (t >= 1 && o != GRU_OOB) ? o - 4u * H : GRU_OOB);
-      v[5][s] = gru_bload(rd, o);
+      for (int p = 0; p < 4; ++p) v[p][s] = m2d_bload(rs[p], o);
+      v[4][s] = m2d_bload(rout, (t >= 1 && o != M2D_OOB) ? o - 4u * H : M2D_OOB);
+      v[5][s] = m2d_bload(rd, o);
     }
   };
   load(cur, T - 1);
@@ -1432,12 +1420,12 @@ __global__ void __launch_bounds__(64) m2d_gru_small_bwd_kernel(const float* __re
 #pragma unroll
     for (int s = 0; s < GRU_SMALL_CH; ++s) {
       const unsigned o = goff(t0 + GRU_SMALL_CH - s);
-      gru_bstore(po[0][s], rgi, o);
-      gru_bstore(po[1][s], rgi, o + 4u * H);
-      gru_bstore(po[2][s], rgi, o + 8u * H);
-      gru_bstore(po[0][s], rgh, o);
-      gru_bstore(po[1][s], rgh, o + 4u * H);
-      gru_bstore(po[3][s], rgh, o + 8u * H);
+      m2d_bstore1(po[0][s], rgi, o);
+      m2d_bstore1(po[1][s], rgi, o + 4u * H);
+      m2d_bstore1(po[2][s], rgi, o + 8u * H);
+      m2d_bstore1(po[0][s], rgh, o);
+      m2d_bstore1(po[1][s], rgh, o + 4u * H);
+      m2d_bstore1(po[3][s], rgh, o + 8u * H);
     }
     load(nxt, t0 - GRU_SMALL_CH);
 #pragma unroll
@@ -1482,19 +1470,19 @@ __global__ void __launch_bounds__(64) m2d_gru_small_bwd_kernel(const float* __re
 #pragma unroll
   for (int s = 0; s < GRU_SMALL_CH; ++s) {
     const unsigned o = goff(tlast - s);
-    gru_bstore(po[0][s], rgi, o);
-    gru_bstore(po[1][s], rgi, o + 4u * H);
-    gru_bstore(po[2][s], rgi, o + 8u * H);
-    gru_bstore(po[0][s], rgh, o);
-    gru_bstore(po[1][s], rgh, o + 4u * H);
-    gru_bstore(po[3][s], rgh, o + 8u * H);
+    m2d_bstore1(po[0][s], rgi, o);
+    m2d_bstore1(po[1][s], rgi, o + 4u * H);
+    m2d_bstore1(po[2][s], rgi, o + 8u * H);
+    m2d_bstore1(po[0][s], rgh, o);
+    m2d_bstore1(po[1][s], rgh, o + 4u * H);
+    m2d_bstore1(po[3][s], rgh, o + 8u * H);
   }
 }
 
 extern "C" {
 
 // the byte extent of every buffer a wave of the small kernels addresses (4 rows x T x 3H floats) stays below 2^30,
-// far from the range-check offset GRU_OOB
+// far from the range-check offset M2D_OOB
 static bool gru_small_fits(int T, int H) { return 4ull * (unsigned long long)T * 3ull * (unsigned long long)H * 4ull < (1ull << 30); }
 
 int m2d_gru_small_fwd(const float* gi, const float* w_hh, const float* b_hh, const int* lengths, float* out,

@@ -8,11 +8,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define M2D_OK 0
-#define M2D_ERR_ARG -1
-#define M2D_ERR_HIP -2
-#define M2D_ERR_WORKSPACE -3
-#define M2D_ERR_RANGE -4
+// the public C-ABI (error codes, struct M2dAdamItem, every entry point): each extern "C" definition is compiled against
+// its declaration, so one that disagrees with the header is a "conflicting types" error
+#include "../../include/m2d.h"
 
 void m2d_set_error(const char* fmt, ...);
 
@@ -47,18 +45,6 @@ struct M2dProfScope {
                int d1 = 0, int d2 = 0);
   ~M2dProfScope();
 };
-
-// one tensor of a multi-tensor Adam step: struct M2dAdamItem of include/m2d.h (kept identical)
-typedef struct M2dAdamItem {
-  float* param;
-  const float* grad;
-  float* exp_avg;
-  float* exp_avg_sq;
-  long long numel;
-  float* pack_fwd;
-  float* pack_bwd;
-  int cout, cin, ks, reserved;
-} M2dAdamItem;
 
 // The fused activation of every epilogue (act: 0 none, 1 ReLU, 2 leaky with `slope`). It gives what
 // torch.nn.functional gives on the same fp32 value: NaN -> NaN and +inf -> +inf for every act, -inf -> 0 under ReLU and

@@ -8,10 +8,9 @@
 //   M, N multiples of 128, K a multiple of 16. 128 x 128 x 16 tiles, four waves (2 x 2 of 64 x 64), two LDS stages filled
 //   by 16-byte LDS-DMA, fragments of two neighbouring 32-row blocks interleaved (one 8-byte LDS read feeds two MFMAs).
 #include "m2d_common.h"
+#include "m2d_device.h"
 
-typedef float pg_f32x16 __attribute__((ext_vector_type(16)));
 typedef float pg_f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) float pg_lds_f;
 
 // [0] s_memrealtime (100 MHz) and [1] s_memtime (shader clock) at kernel entry of workgroup 0, [2] / [3] at its end
 __device__ unsigned long long m2d_probe_clock_buf[4];
@@ -40,8 +39,8 @@ __global__ void __launch_bounds__(256, 1) m2d_probe_gemm_kernel(const float* __r
     by = first + rem - bx * gsz;
   }
   const int m0 = by * BM, n0 = bx * BN;
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)A, (short)0, (int)((size_t)M * K * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)B, (short)0, (int)((size_t)N * K * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = m2d_rsrc(A, (unsigned)((size_t)M * K * 4));
+  const __amdgpu_buffer_rsrc_t rb = m2d_rsrc(B, (unsigned)((size_t)N * K * 4));
   unsigned offa[2], offb[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -53,11 +52,11 @@ __global__ void __launch_bounds__(256, 1) m2d_probe_gemm_kernel(const float* __r
     const int sa = k0 * M * 4, sb = k0 * N * 4;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (pg_lds_f*)(st + (wave + 4 * i) * PF), 16, (int)offa[i], sa, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (pg_lds_f*)(st + BK * BM + (wave + 4 * i) * PF), 16, (int)offb[i], sb, 0, 0);
+      m2d_bload_lds<16>(ra, st + (wave + 4 * i) * PF, offa[i], sa);
+      m2d_bload_lds<16>(rb, st + BK * BM + (wave + 4 * i) * PF, offb[i], sb);
     }
   };
-  pg_f32x16 acc[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll

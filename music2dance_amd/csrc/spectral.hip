@@ -28,6 +28,7 @@
 // Frame t's value depends on t, its samples, the basis and the bands only: the tile size F is a function of (hop, n_fft,
 // nb), the lane a frame lands in changes no operation. No atomics.
 #include "m2d_common.h"
+#include "m2d_device.h"
 #include "m2d_reduce.h"
 
 #include <limits.h>
@@ -41,9 +42,6 @@
 #define M2D_BA_THREADS 1024
 #define M2D_BA_MAX_T 16384
 #define M2D_BA_MAX_R 64
-
-typedef float sp_f32x16 __attribute__((ext_vector_type(16)));
-typedef float sp_f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -87,18 +85,18 @@ __global__ void __launch_bounds__(M2D_SP_THREADS) m2d_stft_bands_kernel(
 
   const float* xl = xs + (l31 < F ? l31 : 0) * (hop + pad);   // lanes past the tile recompute frame 0 (not stored)
   const int NT = n >> 6, NC = n >> 5, nbins = n / 2 + 1;
-  sp_f32x16 eacc[4];
+  f32x16 eacc[4];
 #pragma unroll
   for (int bt = 0; bt < 4; ++bt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) eacc[bt][r] = 0.f;
 
   for (int tb = w; tb < NT; tb += M2D_SP_WAVES) {
-    sp_f32x16 re, im;
+    f32x16 re, im;
 #pragma unroll
     for (int r = 0; r < 16; ++r) re[r] = im[r] = 0.f;
-    const sp_f32x4* img = reinterpret_cast<const sp_f32x4*>(image) + (size_t)tb * NC * 512 + lane;
-    sp_f32x4 cur[8], nxt[8];
+    const m2d_f32x4* img = reinterpret_cast<const m2d_f32x4*>(image) + (size_t)tb * NC * 512 + lane;
+    m2d_f32x4 cur[8], nxt[8];
 #pragma unroll
     for (int v = 0; v < 8; ++v) nxt[v] = cur[v] = img[v * 64];
     for (int c = 0; c < NC; ++c) {

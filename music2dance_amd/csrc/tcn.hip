@@ -1,31 +1,11 @@
 // TemporalBlock convolution kernels for gfx950 (see tcn.h for what they are and why they exist).
 #include "tcn.h"
+#include "m2d_device.h"
 
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float tcn_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) float tcn_lds_f;
-
-// a byte offset the buffer range check always rejects: loads return 0.0, LDS-DMA writes 0.0, stores are dropped
-#define TCN_OOB 0x80000000u
-
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t tcn_rsrc(const void* p, unsigned nbytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)nbytes, 0x00020000);
-}
-// global -> LDS without a register stop: lane l of the wave writes dst[l * BYTES / 4 ..] (dst wave-uniform)
-template <int BYTES>
-static __device__ __forceinline__ void tcn_dma(__amdgpu_buffer_rsrc_t r, float* dst, unsigned voff, int soff) {
-  if constexpr (BYTES == 16) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (tcn_lds_f*)dst, 16, (int)voff, soff, 0, 0);
-  else __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (tcn_lds_f*)dst, 4, (int)voff, soff, 0, 0);
-}
-static __device__ __forceinline__ float tcn_bload(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, 0));
-}
-static __device__ __forceinline__ unsigned tcn_lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const float*)p;
-}
+// (the tcn_ds_read / tcn_wait_* helpers below belong to these kernels' schedule and stay here, not in m2d_device.h)
 // LDS reads the compiler does not see as memory accesses (it would put `s_waitcnt vmcnt(0)` in front of a ds_read
 // while an LDS-DMA into ANOTHER stage is in flight); their completion is waited for explicitly (tcn_wait_*)
 template <int OFF>
@@ -87,15 +67,6 @@ static __device__ __forceinline__ void tcn_static_for(F&& f) {
     f(std::integral_constant<int, I>{});
     tcn_static_for<I + 1, N>(f);
   }
-}
-
-// n / d, n % d for 0 <= n < 2^24 (exact in fp32)
-static __device__ __forceinline__ void tcn_divmod(int n, int d, float inv, int& q, int& r) {
-  q = (int)((float)n * inv);
-  r = n - q * d;
-  const int adj = (r < 0 ? -1 : 0) + (r >= d ? 1 : 0);
-  q += adj;
-  r -= adj * d;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -177,13 +148,13 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
   TCN_STAMP_AT(0);
   const int p0 = blockIdx.x * NT;                  // first flattened position of the tile
   int n0, o0;
-  tcn_divmod(p0, L, L_inv, n0, o0);
+  m2d_divmod(p0, L, L_inv, n0, o0);
   const int j1 = L - o0;                           // first tile column of the second sample (>= NT: none)
 
   // ---- weights: chunk c = (channel block cb, tap t). A wave's A fragments of a chunk are 8 channels (its K half) x its 32
   // output channels = 1 KB = ONE 16-byte LDS-DMA instruction: every wave streams exactly what it reads into a ring of
   // its own, As[wave][c % NS][8][32] - nobody else touches it, so the main loop needs no barrier at all.
-  const __amdgpu_buffer_rsrc_t rw = tcn_rsrc(p.wimg, (unsigned)((size_t)Cin * KS * 128 * sizeof(float)));
+  const __amdgpu_buffer_rsrc_t rw = m2d_rsrc(p.wimg, (unsigned)((size_t)Cin * KS * 128 * sizeof(float)));
   const int a_krow = kh * 8 + (lane >> 3);         // the chunk's channel this lane fetches
   // (16-wide blocks: odd channel rows of the stage are stored rotated by 16 columns - lanes k and k + 1 of a fragment read
   // then hit disjoint banks; the rotation is made HERE, on the source address: the LDS side of a DMA is lane-linear)
@@ -194,13 +165,13 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
   auto issue_a = [&](int c, int cb, int t) {
     const int tap = p.tap_rev ? KS - 1 - t : t;
     const int soff = ((cb * 16 * KS + tap) * 128) * 4;
-    const unsigned voff = (cb * 16 + a_krow < Cin && c < nch) ? a_voff : TCN_OOB;
-    tcn_dma<16>(rw, Aw + (c & (NS - 1)) * 256, voff, soff);
+    const unsigned voff = (cb * 16 + a_krow < Cin && c < nch) ? a_voff : M2D_OOB;
+    m2d_bload_lds<16>(rw, Aw + (c & (NS - 1)) * 256, voff, soff);
   };
 
   // ---- activation tile with halo -> Xs -------------------------------------------------------------------------------
   {
-    const __amdgpu_buffer_rsrc_t rx = tcn_rsrc(p.x, (unsigned)((size_t)p.B * Cin * L * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t rx = m2d_rsrc(p.x, (unsigned)((size_t)p.B * Cin * L * sizeof(float)));
     const int nelem = ncb * 16 * LDX;
     auto src_off = [&](int e) -> unsigned {
       const int c = e / LDX;                       // (constant divisor)
@@ -209,21 +180,21 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
       const int l = second ? col - (j1 + KS - 1) - PAD : o0 + col - PAD;
       const int n = n0 + (second ? 1 : 0);
       const bool ok = (unsigned)l < (unsigned)L && n < p.B && c < Cin && e < nelem;
-      return ok ? (unsigned)(((n * Cin + c) * L + l) * 4) : TCN_OOB;
+      return ok ? (unsigned)(((n * Cin + c) * L + l) * 4) : M2D_OOB;
     };
     if constexpr (!XMASK) {
-      for (int e0 = wave * 64; e0 < xs_alloc; e0 += 512) tcn_dma<4>(rx, Xs + e0, src_off(e0 + lane), 0);
+      for (int e0 = wave * 64; e0 < xs_alloc; e0 += 512) m2d_bload_lds<4>(rx, Xs + e0, src_off(e0 + lane), 0);
     } else {
-      const __amdgpu_buffer_rsrc_t rm = tcn_rsrc(p.x_mask, (unsigned)((size_t)p.B * Cin * L * sizeof(float)));
+      const __amdgpu_buffer_rsrc_t rm = m2d_rsrc(p.x_mask, (unsigned)((size_t)p.B * Cin * L * sizeof(float)));
       const float ms = p.x_mask_slope;
       for (int e0 = tid; e0 < xs_alloc; e0 += 512 * 8) {
         float v[8], m[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const int e = e0 + i * 512;
-          const unsigned off = e < xs_alloc ? src_off(e) : TCN_OOB;
-          v[i] = tcn_bload(rx, off);
-          m[i] = tcn_bload(rm, off);
+          const unsigned off = e < xs_alloc ? src_off(e) : M2D_OOB;
+          v[i] = m2d_bload(rx, off);
+          m[i] = m2d_bload(rm, off);
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -244,14 +215,14 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
     const int m = rb * CB + lc;
-    a_base[rb] = tcn_lds_addr(Aw) + (unsigned)((lk * 32 + (CB == 32 ? m : (m ^ (16 * (lk & 1))))) * 4);
+    a_base[rb] = m2d_lds_addr(Aw) + (unsigned)((lk * 32 + (CB == 32 ? m : (m ^ (16 * (lk & 1))))) * 4);
   }
   // B (activations): Xs[16 cb + 8 kh + KD s + lk][colmap(CB jb + lc) + t]
   unsigned b_base[TN];
 #pragma unroll
   for (int jb = 0; jb < TN; ++jb) {
     const int j = jb * CB + lc;
-    b_base[jb] = tcn_lds_addr(Xs) + (unsigned)(((kh * 8 + lk) * LDX + j + (j >= j1 ? KS - 1 : 0)) * 4);
+    b_base[jb] = m2d_lds_addr(Xs) + (unsigned)(((kh * 8 + lk) * LDX + j + (j >= j1 ? KS - 1 : 0)) * 4);
   }
 
   acc_t acc[RB][TN];
@@ -351,21 +322,21 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
   constexpr int NPC = 128 * PPR / 512;           // pieces per thread
   unsigned eoff[NPC];                            // element offset of the piece, or ~0u
   int erow[NPC];
-  tcn_f32x4 emk[NPC], ers[NPC];
+  m2d_f32x4 emk[NPC], ers[NPC];
 #pragma unroll
   for (int i = 0; i < NPC; ++i) {
     const int q = tid + 512 * i;
     const int row = q / PPR, c4 = q - row * PPR;
     const int pos = p0 + 4 * c4;
     int n, l;
-    tcn_divmod(pos < Ntot ? pos : 0, L, L_inv, n, l);
+    m2d_divmod(pos < Ntot ? pos : 0, L, L_inv, n, l);
     erow[i] = row * (Cfg::LDE) + 4 * c4;
     eoff[i] = pos < Ntot ? (unsigned)((n * 128 + row) * L + l) : 0xffffffffu;
-    emk[i] = tcn_f32x4{1.f, 1.f, 1.f, 1.f};
-    ers[i] = tcn_f32x4{0.f, 0.f, 0.f, 0.f};
+    emk[i] = m2d_f32x4{1.f, 1.f, 1.f, 1.f};
+    ers[i] = m2d_f32x4{0.f, 0.f, 0.f, 0.f};
     if (eoff[i] != 0xffffffffu) {
-      if (p.out_mask) emk[i] = *reinterpret_cast<const tcn_f32x4*>(p.out_mask + ((p.out_mask_wrap && eoff[i] >= p.out_mask_wrap) ? eoff[i] - p.out_mask_wrap : eoff[i]));
-      if (p.residual) ers[i] = *reinterpret_cast<const tcn_f32x4*>(p.residual + eoff[i]);
+      if (p.out_mask) emk[i] = *reinterpret_cast<const m2d_f32x4*>(p.out_mask + ((p.out_mask_wrap && eoff[i] >= p.out_mask_wrap) ? eoff[i] - p.out_mask_wrap : eoff[i]));
+      if (p.residual) ers[i] = *reinterpret_cast<const m2d_f32x4*>(p.residual + eoff[i]);
     }
   }
   // the two K halves meet: E[kh][m][LDE] over the (now free) loop memory, added on the way out
@@ -390,12 +361,12 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
 #pragma unroll
     for (int i = 0; i < NPC; ++i) {
       if (eoff[i] == 0xffffffffu) continue;
-      tcn_f32x4 v = *reinterpret_cast<const tcn_f32x4*>(smem + erow[i]) +
-                    *reinterpret_cast<const tcn_f32x4*>(smem + 128 * LDE + erow[i]);
+      m2d_f32x4 v = *reinterpret_cast<const m2d_f32x4*>(smem + erow[i]) +
+                    *reinterpret_cast<const m2d_f32x4*>(smem + 128 * LDE + erow[i]);
       if (p.bias) v += p.bias[(tid + 512 * i) / PPR];
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = m2d_act(v[j], p.act, p.slope);
-      tcn_f32x4 mk = {1.f, 1.f, 1.f, 1.f};
+      m2d_f32x4 mk = {1.f, 1.f, 1.f, 1.f};
       if (has_mask) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) mk[j] = emk[i][j] > 0.f ? 1.f : ms;
@@ -405,12 +376,12 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_conv_kernel(const M2dTcnConv p
       } else {
         v *= mk;
         if (p.residual) {
-          const tcn_f32x4 sum = v + ers[i];
-          if (p.sum_out) *reinterpret_cast<tcn_f32x4*>(p.sum_out + eoff[i]) = sum;
+          const m2d_f32x4 sum = v + ers[i];
+          if (p.sum_out) *reinterpret_cast<m2d_f32x4*>(p.sum_out + eoff[i]) = sum;
           else v = sum;
         }
       }
-      *reinterpret_cast<tcn_f32x4*>(p.out + eoff[i]) = v;
+      *reinterpret_cast<m2d_f32x4*>(p.out + eoff[i]) = v;
     }
   }
 #ifdef M2D_STAMP
@@ -570,9 +541,9 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_wgrad_kernel(const M2dTcnWgrad
   const int ck0 = run * cpw;
   const int ck1 = ck0 + cpw < nck ? ck0 + cpw : nck;
 
-  const __amdgpu_buffer_rsrc_t rdy = tcn_rsrc(p.dy, (unsigned)((size_t)p.B * 128 * L * sizeof(float)));
-  const __amdgpu_buffer_rsrc_t rmk = tcn_rsrc(DMASK ? p.dy_mask : p.dy, DMASK ? (unsigned)((size_t)p.B * 128 * L * sizeof(float)) : 0u);
-  const __amdgpu_buffer_rsrc_t rx = tcn_rsrc(p.x, (unsigned)((size_t)p.B * Cin * L * sizeof(float)));
+  const __amdgpu_buffer_rsrc_t rdy = m2d_rsrc(p.dy, (unsigned)((size_t)p.B * 128 * L * sizeof(float)));
+  const __amdgpu_buffer_rsrc_t rmk = m2d_rsrc(DMASK ? p.dy_mask : p.dy, DMASK ? (unsigned)((size_t)p.B * 128 * L * sizeof(float)) : 0u);
+  const __amdgpu_buffer_rsrc_t rx = m2d_rsrc(p.x, (unsigned)((size_t)p.B * Cin * L * sizeof(float)));
 
   // ---- staging maps: dy in 16-byte pieces (128 rows x 15), x in dwords (32 rows x XW) ---------------------------------
   constexpr int NDY = (128 * (KC / 4) + 511) / 512;  // 4
@@ -585,7 +556,7 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_wgrad_kernel(const M2dTcnWgrad
   for (int i = 0; i < NDY; ++i) {
     const int e = tid + 512 * i;
     const int row = e / (KC / 4), c4 = e - row * (KC / 4);
-    dy_off[i] = e < 128 * (KC / 4) ? (unsigned)((row * L + 4 * c4) * 4) : TCN_OOB;
+    dy_off[i] = e < 128 * (KC / 4) ? (unsigned)((row * L + 4 * c4) * 4) : M2D_OOB;
     dy_lds[i] = e < 128 * (KC / 4) ? row * LDD + 4 * c4 : Cfg::STAGE_DATA;   // (idle lanes: the stage's dummy tail - no branch)
   }
 #pragma unroll
@@ -593,34 +564,34 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_wgrad_kernel(const M2dTcnWgrad
     const int e = tid + 512 * i;
     const int ci = e / XW, col = e - ci * XW;
     const bool ok = e < 32 * XW && cg * 32 + ci < Cin;
-    x_off[i] = ok ? (unsigned)(((cg * 32 + ci) * L) * 4) : TCN_OOB;
+    x_off[i] = ok ? (unsigned)(((cg * 32 + ci) * L) * 4) : M2D_OOB;
     x_col[i] = col - PAD;
     x_lds[i] = e < 32 * XW ? 128 * LDD + ci * LDXW + col : Cfg::STAGE_DATA + 4;
   }
-  tcn_f32x4 rdv[NDY], rmv[DMASK ? NDY : 1];
+  m2d_f32x4 rdv[NDY], rmv[DMASK ? NDY : 1];
   float rxv[NX];
   auto load_chunk = [&](int ck) {
     const int n = ck / cpl, lc0 = (ck - n * cpl) * KC;
     const unsigned dbase = (unsigned)((n * 128 * L + lc0) * 4);
 #pragma unroll
     for (int i = 0; i < NDY; ++i) {
-      const unsigned off = dy_off[i] != TCN_OOB ? dy_off[i] + dbase : TCN_OOB;
-      rdv[i] = __builtin_bit_cast(tcn_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rdy, (int)off, 0, 0));
-      if constexpr (DMASK) rmv[i] = __builtin_bit_cast(tcn_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rmk, (int)off, 0, 0));
+      const unsigned off = dy_off[i] != M2D_OOB ? dy_off[i] + dbase : M2D_OOB;
+      rdv[i] = m2d_bload16(rdy, off);
+      if constexpr (DMASK) rmv[i] = m2d_bload16(rmk, off);
     }
     const unsigned xbase = (unsigned)((n * Cin * L) * 4);
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
       const int l = lc0 + x_col[i];
-      const bool ok = x_off[i] != TCN_OOB && (unsigned)l < (unsigned)L;
-      rxv[i] = tcn_bload(rx, ok ? x_off[i] + xbase + (unsigned)(l * 4) : TCN_OOB);
+      const bool ok = x_off[i] != M2D_OOB && (unsigned)l < (unsigned)L;
+      rxv[i] = m2d_bload(rx, ok ? x_off[i] + xbase + (unsigned)(l * 4) : M2D_OOB);
     }
   };
   auto store_chunk = [&](float* st) {
     const float ms = p.dy_mask_slope;
 #pragma unroll
     for (int i = 0; i < NDY; ++i) {
-      tcn_f32x4 v = rdv[i];
+      m2d_f32x4 v = rdv[i];
       if constexpr (DMASK) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] *= (rmv[i][j] > 0.f ? 1.f : ms);
@@ -644,8 +615,8 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_wgrad_kernel(const M2dTcnWgrad
 
   // fragment addresses inside a stage: A = dy image [m][k], m = 32 wr + l31, k = 30 kh + 2 s + lh;
   //                                    B = x image [c][k + t], c = l31
-  const unsigned a_base = tcn_lds_addr(smem) + (unsigned)(((wr * 32 + l31) * LDD + kh * (2 * NSTEP) + lh) * 4);
-  const unsigned b_base = tcn_lds_addr(smem) + (unsigned)((128 * LDD + l31 * LDXW + kh * (2 * NSTEP) + lh) * 4);
+  const unsigned a_base = m2d_lds_addr(smem) + (unsigned)(((wr * 32 + l31) * LDD + kh * (2 * NSTEP) + lh) * 4);
+  const unsigned b_base = m2d_lds_addr(smem) + (unsigned)((128 * LDD + l31 * LDXW + kh * (2 * NSTEP) + lh) * 4);
 
   if (ck0 < ck1) {
     load_chunk(ck0);
@@ -738,27 +709,27 @@ __global__ void __launch_bounds__(512, 1) m2d_tcn_wgrad_kernel(const M2dTcnWgrad
 
   // ---- the two K halves meet in LDS; the sum leaves as the accumulator image [tap][reg quad][wr][lane] x float4 -------
   TCN_STAMP_AT(2);
-  tcn_f32x4* R = reinterpret_cast<tcn_f32x4*>(smem);
+  m2d_f32x4* R = reinterpret_cast<m2d_f32x4*>(smem);
   __syncthreads();
   if (kh == 1) {
 #pragma unroll
     for (int t = 0; t < KS; ++t)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        tcn_f32x4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
+        m2d_f32x4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
         R[(t * 4 + q) * 256 + wr * 64 + lane] = v;
       }
   }
   __syncthreads();
   float* part = slab + (size_t)(run * gridDim.x + cg) * Cfg::part_floats();
   if (kh == 0) {
-    tcn_f32x4* dst = reinterpret_cast<tcn_f32x4*>(part);
+    m2d_f32x4* dst = reinterpret_cast<m2d_f32x4*>(part);
 #pragma unroll
     for (int t = 0; t < KS; ++t)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const tcn_f32x4 o = R[(t * 4 + q) * 256 + wr * 64 + lane];
-        tcn_f32x4 v = {acc[t][4 * q] + o[0], acc[t][4 * q + 1] + o[1], acc[t][4 * q + 2] + o[2], acc[t][4 * q + 3] + o[3]};
+        const m2d_f32x4 o = R[(t * 4 + q) * 256 + wr * 64 + lane];
+        m2d_f32x4 v = {acc[t][4 * q] + o[0], acc[t][4 * q + 1] + o[1], acc[t][4 * q + 2] + o[2], acc[t][4 * q + 3] + o[3]};
         dst[(t * 4 + q) * 256 + wr * 64 + lane] = v;
       }
   }
@@ -784,7 +755,7 @@ template <int KS>
 __global__ void __launch_bounds__(256) m2d_tcn_wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw,
                                                                      float* __restrict__ dbias, int nr, int Cin) {
   using Cfg = TcnWgradCfg<KS>;
-  __shared__ tcn_f32x4 sh[3][64];
+  __shared__ m2d_f32x4 sh[3][64];
   const int cg = blockIdx.x, ncg = gridDim.x;
   const size_t pf = Cfg::part_floats();
   const int tid = threadIdx.x;
@@ -810,8 +781,8 @@ __global__ void __launch_bounds__(256) m2d_tcn_wgrad_reduce_kernel(const float* 
   const int qt = tid >> 6;                      // quarter of the runs
   const int per = (nr + 3) >> 2;
   const int r0 = qt * per, r1 = r0 + per < nr ? r0 + per : nr;
-  tcn_f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  const tcn_f32x4* src = reinterpret_cast<const tcn_f32x4*>(slab + (size_t)cg * pf) + u;
+  m2d_f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  const m2d_f32x4* src = reinterpret_cast<const m2d_f32x4*>(slab + (size_t)cg * pf) + u;
   const size_t stride4 = (size_t)ncg * pf / 4;
 #pragma unroll 8
   for (int r = r0; r < r1; ++r) s += src[(size_t)r * stride4];
