@@ -558,6 +558,30 @@ size_t m2d_pairwise_mean_dist_workspace_bytes(int G, int K);
 int m2d_pairwise_mean_dist(const float* X, long long ldx, int G, int K, int D, double* out, void* ws, size_t ws_bytes,
                            void* stream);
 
+/* ---- audio-motion synchronisation of a take (metrics.py; no counterpart in the reference) ----
+ * out[b T + t] = g(c[b], sigma)[t], the smoothing of m2d_beat_align (the same device function: bit-equal to its
+ * onset_smooth / speed_smooth for the same row and sigma), for c (B, T) contiguous of ANY length T >= 0.
+ * M2D_ERR_ARG (nothing launched): B <= 0, T < 0, sigma <= 0 or ceil(3 sigma) > 64, a null pointer. */
+int m2d_gauss_smooth(const float* c, int B, int T, double sigma, float* out, void* stream);
+/* Lag / tempo-factor profile. a (B, Ta) and b (B, Tb) fp32, rows lda / ldb floats apart; na_rows / nb_rows: optional
+ * DEVICE int32 (B) lengths of the rows (NULL: Ta / Tb for every row). For row b with na frames of a and nb of b, factor
+ * f = factors[i] (F HOST doubles) and integer lag l in [-L, L], take every j in [0, na) with x = (double)(j + l) / f in
+ * [0, nb - 1] and pair a[j] with bv = b[i] + fr (b[min(i + 1, nb - 1)] - b[i]), i = floor(x), fr = x - i, in fp64
+ * from the fp32 values (f == 1: b[j + l] exactly). n = the number of pairs;
+ *   r = S_ab / sqrt(S_aa S_bb), two passes in fp64: the means of the pairs, then the sums of the centred products;
+ *   r = NaN when n < min_overlap or S_aa or S_bb is 0. l > 0: the motion (b) lags the audio (a) by l frames.
+ * r (B, F, 2 L + 1) double and n (B, F, 2 L + 1) int32, lag l at index l + L. One wave a cell: lane k sums the j = k
+ * (mod 64) in ascending j, the 64 partials are added by the butterfly 32, 16, .., 1: r and n are bit-level pure
+ * functions of the row's values, na, nb, f, l and min_overlap - not of B, F, L, the strides or the launch. No atomics,
+ * no workspace. A length of 0 gives NaN and n = 0.
+ * M2D_ERR_ARG (nothing launched): B or F <= 0; L < 0; a factor not finite or <= 0; min_overlap < 2; Ta or Tb < 0 or
+ * above max_frames (16384); a row length outside [0, T] (read back with one small copy, except inside a stream capture,
+ * where such a row counts as empty); lda < Ta or ldb < Tb; a null or misaligned pointer. */
+int m2d_sync_scan_max_frames(void);
+int m2d_sync_scan(const float* a, long long lda, const int* na_rows, const float* b, long long ldb, const int* nb_rows,
+                  int B, int Ta, int Tb, const double* factors, int F, int L, int min_overlap, double* r, int* n,
+                  void* stream);
+
 /* ---- nearest-neighbour queries between two sets of rows (metrics.py; no counterpart in the
  * reference) -------------------------------------------------------------------------------------------------------
  * Rows are fp32 vectors of dimension D in [1, 128], ld* floats apart (a column block of a wider buffer is taken in

@@ -141,6 +141,10 @@ SIGNATURES = {
     "m2d_frechet": (_I, [_F, _F, _F, _F, _I, _I, _F, _F, _S, _F]),
     "m2d_pairwise_mean_dist_workspace_bytes": (_S, [_I, _I]),
     "m2d_pairwise_mean_dist": (_I, [_F, _c.c_longlong, _I, _I, _I, _F, _F, _S, _F]),
+    "m2d_gauss_smooth": (_I, [_F, _I, _I, _c.c_double, _F, _F]),
+    "m2d_sync_scan_max_frames": (_I, []),
+    "m2d_sync_scan": (_I, [_F, _c.c_longlong, _F, _F, _c.c_longlong, _F, _I, _I, _I, _c.POINTER(_c.c_double), _I, _I, _I,
+                           _F, _F, _F]),
     "m2d_knn_max_k": (_I, []),
     "m2d_knn_radii_workspace_bytes": (_S, [_I, _I]),
     "m2d_knn_radii": (_I, [_F, _c.c_longlong, _I, _I, _I, _F, _F, _S, _F]),

@@ -2,7 +2,9 @@
 //   m2d_stft_bands    band energies of STFT frames, the DFT as an fp32-MFMA contraction with the band projection fused;
 //   m2d_onset_flux    log-compressed, half-wave rectified spectral flux of the band energies;
 //   m2d_motion_speed  mean joint speed of a dance;
-//   m2d_beat_align    smoothing, event detection, nearest-event distances and the two scores, one workgroup per row.
+//   m2d_beat_align    smoothing, event detection, nearest-event distances and the two scores, one workgroup per row;
+//   m2d_gauss_smooth  that smoothing alone, for curves of any length;
+//   m2d_sync_scan     Pearson correlation of two curves over a grid of lags and time-scale factors.
 //
 // m2d_stft_bands. A workgroup owns one row and a tile of F <= 32 consecutive frames. Their windows overlap, so the
 // tile's samples are staged ONCE in LDS as one span of (F - 1) hop + n_fft floats (32 frames at hop 640, n_fft 1024:
@@ -42,6 +44,12 @@
 #define M2D_BA_THREADS 1024
 #define M2D_BA_MAX_T 16384
 #define M2D_BA_MAX_R 64
+#define M2D_GS_THREADS 256
+#define M2D_SS_THREADS 1024
+#define M2D_SS_WAVES 16
+#define M2D_SS_LAGS 64      // lags of one (row, factor) a workgroup takes: 4 a wave
+#define M2D_SS_MAX_T 16384
+#define M2D_SS_MAX_F 32     // factors of one launch (a kernel argument); more go in further launches
 
 namespace {
 
@@ -211,25 +219,36 @@ __device__ void ba_scan_max(int* sc) {   // inclusive, over the M2D_BA_THREADS e
   }
 }
 
-// sm[t] = g(c, sigma)[t] in fp64, rounded once; mask[t] = event; -> the number of events
+// The smoothing g(c, sigma) of m2d_beat_align and m2d_gauss_smooth, stated once. ba_weights: wt[j + R] = w_j for j in
+// [-R, R], by the first `threads` threads of the workgroup (the caller syncs afterwards). ba_smooth_at: g(c, sigma)[t],
+// fp64 sums in ascending j, one rounding to fp32.
+__device__ __forceinline__ void ba_weights(double* wt, double sigma, int R, int threads) {
+  for (int j = threadIdx.x; j <= 2 * R; j += threads)
+    wt[j] = exp(-(double)((j - R) * (j - R)) / (2.0 * sigma * sigma));
+}
+
+__device__ __forceinline__ float ba_smooth_at(const float* __restrict__ c, int T, int t, int R, const double* wt) {
+  double num = 0.0, den = 0.0;
+  for (int j = -R; j <= R; ++j) {
+    const int u = t + j;
+    if (u >= 0 && u < T) {
+      num += wt[j + R] * (double)c[u];
+      den += wt[j + R];
+    }
+  }
+  return (float)(num / den);
+}
+
+// sm[t] = g(c, sigma)[t]; mask[t] = event; -> the number of events
 __device__ int ba_curve(const float* __restrict__ c, int T, double sigma, int R, bool music, float* sm,
                         unsigned char* mask, double* wt, double* redd, float* out_sm, unsigned char* out_mask, int lo,
                         int hi) {
   const int tid = threadIdx.x;
   __syncthreads();
-  for (int j = tid; j <= 2 * R; j += M2D_BA_THREADS)
-    wt[j] = exp(-(double)((j - R) * (j - R)) / (2.0 * sigma * sigma));
+  ba_weights(wt, sigma, R, M2D_BA_THREADS);
   __syncthreads();
   for (int t = tid; t < T; t += M2D_BA_THREADS) {
-    double num = 0.0, den = 0.0;
-    for (int j = -R; j <= R; ++j) {
-      const int u = t + j;
-      if (u >= 0 && u < T) {
-        num += wt[j + R] * (double)c[u];
-        den += wt[j + R];
-      }
-    }
-    const float r = (float)(num / den);
+    const float r = ba_smooth_at(c, T, t, R, wt);
     sm[t] = r;
     if (out_sm) out_sm[t] = r;
   }
@@ -315,6 +334,108 @@ __global__ void __launch_bounds__(M2D_BA_THREADS) m2d_beat_align_kernel(
     cover = (float)(ba_nearest(maskK, maskM, dist, sc, redd, sa, lo, hi) / (double)nM);
   }
   if (tid < 4) scores[(size_t)blockIdx.x * 4 + tid] = tid == 0 ? align : tid == 1 ? cover : tid == 2 ? (float)nK : (float)nM;
+}
+
+// ---- m2d_gauss_smooth: g(c, sigma) row by row, the expression of ba_curve --------------------------------------------
+__global__ void __launch_bounds__(M2D_GS_THREADS) m2d_gauss_smooth_kernel(const float* __restrict__ c, int T, int tiles,
+                                                                          double sigma, int R, float* __restrict__ out) {
+  __shared__ double wt[2 * M2D_BA_MAX_R + 2];
+  const int row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
+  ba_weights(wt, sigma, R, M2D_GS_THREADS);
+  __syncthreads();
+  const int t = tile * M2D_GS_THREADS + threadIdx.x;
+  if (t < T) out[(size_t)row * T + t] = ba_smooth_at(c + (size_t)row * T, T, t, R, wt);
+}
+
+// ---- m2d_sync_scan: the lag / tempo-factor profile of two curves -------------------------------
+// A workgroup owns one row, one factor and M2D_SS_LAGS consecutive lags; it stages the row's a and b in LDS once and its
+// 16 waves take the lags in turn. ONE wave computes a cell: lane k owns the residue class j = k (mod 64), walks it in
+// ascending j with fp64 accumulators, and the 64 partials are added by the xor butterfly 32, 16, 8, 4, 2, 1 (every lane
+// ends with the same bits). Pass 1: n and the two sums; pass 2: the three centred sums, the pairs rebuilt by the same
+// operations. Which wave or workgroup a cell lands in changes no operation: r and n are functions of the row's values,
+// na, nb, f, l and min_overlap alone.
+struct SsFactors {
+  double f[M2D_SS_MAX_F];
+};
+
+__device__ __forceinline__ double ss_wave_sum(double v) {
+  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+  return v;
+}
+
+// the pair of a[j]: x = (j + l) / f; false once x has left [0, nb - 1] (x grows with j; the callers start at j + l >= 0)
+__device__ __forceinline__ bool ss_pair(const float* bs, int nb, double f, long long jl, double& bv) {
+  const double x = (double)jl / f;
+  if (!(x <= (double)(nb - 1))) return false;
+  const int i = (int)x;
+  const double fr = x - (double)i;
+  const double b0 = (double)bs[i], b1 = (double)bs[i + 1 < nb ? i + 1 : nb - 1];
+  bv = b0 + fr * (b1 - b0);
+  return true;
+}
+
+__global__ void __launch_bounds__(M2D_SS_THREADS) m2d_sync_scan_kernel(
+    const float* __restrict__ a, long long lda, const int* __restrict__ na_rows, const float* __restrict__ b,
+    long long ldb, const int* __restrict__ nb_rows, int Ta, int Tb, SsFactors fac, int f0, int F, int L, int chunks,
+    int min_overlap, double* __restrict__ r, int* __restrict__ n) {
+  extern __shared__ float ssh[];
+  float* as = ssh;
+  float* bs = ssh + ((Ta + 3) & ~3);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks, fi = blockIdx.y;
+  int na = na_rows ? na_rows[row] : Ta, nb = nb_rows ? nb_rows[row] : Tb;
+  if (na < 0 || na > Ta || nb < 0 || nb > Tb) na = nb = 0;   // (refused on the host; under a capture: an empty row)
+  const float* arow = a + (long long)row * lda;
+  const float* brow = b + (long long)row * ldb;
+  for (int i = tid; i < na; i += M2D_SS_THREADS) as[i] = arow[i];
+  for (int i = tid; i < nb; i += M2D_SS_THREADS) bs[i] = brow[i];
+  __syncthreads();
+  const double f = fac.f[fi];
+  const long long cells = 2LL * L + 1;
+  const size_t out0 = ((size_t)row * F + f0 + fi) * (size_t)cells;
+  for (int c = w; c < M2D_SS_LAGS; c += M2D_SS_WAVES) {
+    const long long li = (long long)chunk * M2D_SS_LAGS + c;
+    if (li >= cells) break;
+    const long long l = li - L;
+    // lane's first j: the smallest j = lane (mod 64) with j + l >= 0
+    long long j0 = lane;
+    if (-l > j0) j0 += ((-l - j0 + 63) / 64) * 64;
+    int cnt = 0;
+    double sa = 0.0, sb = 0.0;
+    if (nb > 0) {
+      for (long long j = j0; j < na; j += 64) {
+        double bv;
+        if (!ss_pair(bs, nb, f, j + l, bv)) break;
+        sa += (double)as[j];
+        sb += bv;
+        ++cnt;
+      }
+    }
+    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s);
+    sa = ss_wave_sum(sa);
+    sb = ss_wave_sum(sb);
+    double rv = nan("");
+    if (cnt >= min_overlap) {   // uniform over the wave
+      const double ma = sa / (double)cnt, mb = sb / (double)cnt;
+      double sab = 0.0, saa = 0.0, sbb = 0.0;
+      for (long long j = j0; j < na; j += 64) {
+        double bv;
+        if (!ss_pair(bs, nb, f, j + l, bv)) break;
+        const double da = (double)as[j] - ma, db = bv - mb;
+        sab += da * db;
+        saa += da * da;
+        sbb += db * db;
+      }
+      sab = ss_wave_sum(sab);
+      saa = ss_wave_sum(saa);
+      sbb = ss_wave_sum(sbb);
+      if (saa != 0.0 && sbb != 0.0) rv = sab / sqrt(saa * sbb);
+    }
+    if (lane == 0) {
+      r[out0 + li] = rv;
+      n[out0 + li] = cnt;
+    }
+  }
 }
 
 int sp_nfft_ok(int n) { return n >= 256 && n <= 2048 && (n & (n - 1)) == 0; }
@@ -439,6 +560,92 @@ int m2d_beat_align(const float* onset, const float* speed, int B, int T, double 
                      sigma_onset, Ro, sigma_speed, Rv, (float)sigma_align, scores, motion_events, music_events,
                      onset_smooth, speed_smooth);
   M2D_CHECK_LAUNCH("m2d_beat_align");
+  return M2D_OK;
+}
+
+int m2d_gauss_smooth(const float* c, int B, int T, double sigma, float* out, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0 || T < 0) M2D_FAIL(M2D_ERR_ARG, "m2d_gauss_smooth: B must be positive, T non-negative");
+  if (!(sigma > 0.0)) M2D_FAIL(M2D_ERR_ARG, "m2d_gauss_smooth: sigma must be positive");
+  if (3.0 * sigma > M2D_BA_MAX_R)
+    M2D_FAIL(M2D_ERR_ARG, "m2d_gauss_smooth: a smoothing radius ceil(3 sigma) above %d", M2D_BA_MAX_R);
+  if (T == 0) return M2D_OK;
+  if (!c || !out) M2D_FAIL(M2D_ERR_ARG, "m2d_gauss_smooth: null pointer");
+  const int R = (int)ceil(3.0 * sigma);
+  const long long tiles = m2d_ceil_div64(T, M2D_GS_THREADS);
+  if (tiles * B > 0x7fffffffLL) M2D_FAIL(M2D_ERR_ARG, "m2d_gauss_smooth: too many frames");
+  M2dProfScope prof(M2D_FAM_REDUCE, stream, 4.0 * (double)B * T * (R + 1), 8.0 * (double)B * T, "gauss_smooth", T, R, 0);
+  hipLaunchKernelGGL(m2d_gauss_smooth_kernel, dim3((unsigned)(tiles * B)), dim3(M2D_GS_THREADS), 0, stream, c, T,
+                     (int)tiles, sigma, R, out);
+  M2D_CHECK_LAUNCH("m2d_gauss_smooth");
+  return M2D_OK;
+}
+
+int m2d_sync_scan_max_frames(void) { return M2D_SS_MAX_T; }
+
+// the per-row lengths live on the device: one small copy tells the host whether any leaves [0, T]. Not inside a stream
+// capture (a copy to the host would end it): there the kernel treats such a row as empty.
+static int ss_check_lengths(const int* rows, int B, int T, const char* what, hipStream_t stream) {
+  if (!rows) return M2D_OK;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cap) != hipSuccess) M2D_FAIL(M2D_ERR_HIP, "m2d_sync_scan: cannot query the stream");
+  if (cap != hipStreamCaptureStatusNone) return M2D_OK;
+  int* host = (int*)malloc(sizeof(int) * (size_t)B);
+  if (!host) M2D_FAIL(M2D_ERR_HIP, "m2d_sync_scan: out of host memory");
+  hipError_t e = hipMemcpyAsync(host, rows, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  int bad = -1;
+  if (e == hipSuccess)
+    for (int i = 0; i < B && bad < 0; ++i)
+      if (host[i] < 0 || host[i] > T) bad = i;
+  const int len = bad >= 0 ? host[bad] : 0;
+  free(host);
+  if (e != hipSuccess) M2D_FAIL(M2D_ERR_HIP, "m2d_sync_scan: reading %s failed: %s", what, hipGetErrorString(e));
+  if (bad >= 0) M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: %s[%d] = %d lies outside [0, %d]", what, bad, len, T);
+  return M2D_OK;
+}
+
+int m2d_sync_scan(const float* a, long long lda, const int* na_rows, const float* b, long long ldb, const int* nb_rows,
+                  int B, int Ta, int Tb, const double* factors, int F, int L, int min_overlap, double* r, int* n,
+                  void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0 || F <= 0 || L < 0) M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: B and F must be positive, L non-negative");
+  if (Ta < 0 || Tb < 0) M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: Ta and Tb must be non-negative");
+  if (Ta > M2D_SS_MAX_T || Tb > M2D_SS_MAX_T)
+    M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: at most %d frames a row (got %d and %d)", M2D_SS_MAX_T, Ta, Tb);
+  if (min_overlap < 2) M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: min_overlap must be at least 2 (got %d)", min_overlap);
+  if (lda < Ta || ldb < Tb) M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: lda < Ta or ldb < Tb");
+  if (!factors || !r || !n || (!a && Ta > 0) || (!b && Tb > 0)) M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: null pointer");
+  if (((uintptr_t)a & 3) || ((uintptr_t)b & 3) || ((uintptr_t)na_rows & 3) || ((uintptr_t)nb_rows & 3) ||
+      ((uintptr_t)r & 7) || ((uintptr_t)n & 3))
+    M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: a misaligned pointer");
+  for (int i = 0; i < F; ++i)
+    if (!(factors[i] > 0.0) || !isfinite(factors[i]))
+      M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: factor %d must be positive and finite (got %g)", i, factors[i]);
+  const long long chunks = m2d_ceil_div64(2LL * L + 1, M2D_SS_LAGS);
+  if (chunks * B > 0x7fffffffLL) M2D_FAIL(M2D_ERR_ARG, "m2d_sync_scan: too many lags");
+  int rc = ss_check_lengths(na_rows, B, Ta, "na_rows", stream);
+  if (rc == M2D_OK) rc = ss_check_lengths(nb_rows, B, Tb, "nb_rows", stream);
+  if (rc != M2D_OK) return rc;
+
+  const size_t lds = 4 * ((size_t)((Ta + 3) & ~3) + (size_t)Tb);
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&m2d_sync_scan_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, M2D_SP_LDS_MAX) != hipSuccess)
+      M2D_FAIL(M2D_ERR_HIP, "m2d_sync_scan: cannot raise the dynamic LDS limit");
+    attr_set = true;
+  }
+  M2dProfScope prof(M2D_FAM_REDUCE, stream, 16.0 * (double)B * F * (2.0 * L + 1) * Ta,
+                    4.0 * (double)B * ((double)Ta + Tb) + 12.0 * (double)B * F * (2.0 * L + 1), "sync_scan", Ta, Tb, L);
+  for (int f0 = 0; f0 < F; f0 += M2D_SS_MAX_F) {
+    const int Fc = F - f0 < M2D_SS_MAX_F ? F - f0 : M2D_SS_MAX_F;
+    SsFactors fac;
+    for (int i = 0; i < M2D_SS_MAX_F; ++i) fac.f[i] = i < Fc ? factors[f0 + i] : 1.0;
+    hipLaunchKernelGGL(m2d_sync_scan_kernel, dim3((unsigned)(chunks * B), (unsigned)Fc), dim3(M2D_SS_THREADS), lds,
+                       stream, a, lda, na_rows, b, ldb, nb_rows, Ta, Tb, fac, f0, F, L, (int)chunks, min_overlap, r, n);
+    M2D_CHECK_LAUNCH("m2d_sync_scan");
+  }
   return M2D_OK;
 }
 

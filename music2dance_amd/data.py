@@ -128,17 +128,57 @@ def load_sticks(name):
     return sticks
 
 
-def load_all(name, dance_types, augment=False):
-    """utils.py:165-194: skeleton JSONs, resampled audio tracks, style letters and folder names."""
+SYNC_FILE = "sync.json"
+
+
+def sync_heads(lag_frames, hop):
+    """What an estimated lag removes at the head of a take -> (pose frames, audio samples): lag l > 0, the motion lags
+    the audio by l frames - the first l pose frames go; l < 0 - the first -l hop audio samples go. Frame 0 and
+    sample 0 of what is left belong together."""
+    l = int(lag_frames)
+    return (l, 0) if l > 0 else (0, -l * int(hop))
+
+
+def read_sync(directory):
+    """The take's sync.json (prepare_data --sync) when it exists, is accepted and names a lag; else None"""
+    path = os.path.join(directory, SYNC_FILE)
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        est = json.load(f)
+    return est if est.get("accepted") and est.get("lag_frames") is not None else None
+
+
+def apply_sync(take, music, est):
+    """-> (take, music) with the heads sync_heads(est) names removed ('skeletons', 'center' and 'length' of the take)"""
+    frames, samples = sync_heads(est["lag_frames"], est["hop"])
+    if frames:
+        take = dict(take)
+        for key in ("skeletons", "center"):
+            if key in take:
+                take[key] = take[key][frames:]
+        if "length" in take:
+            take["length"] = len(take["skeletons"])
+    return take, music[samples:]
+
+
+def load_all(name, dance_types, augment=False, sync=False):
+    """utils.py:165-194: skeleton JSONs, resampled audio tracks, style letters and folder names. sync (extension): a
+    take whose folder holds an accepted sync.json is trimmed at its head (apply_sync); the others are left as they are."""
     sticks, musics, labels, dirs = [], [], [], []
     for directory, base in _dance_dirs(name):
         if base[6] not in dance_types:
             continue
         dirs.append(directory)
         labels.append(base[6])
-        musics.append(_read_wav(directory + "/resampled_audio_extract.wav"))
+        music = _read_wav(directory + "/resampled_audio_extract.wav")
         with open(directory + _skeleton_file(base)) as f:
-            sticks.append(json.load(f))
+            take = json.load(f)
+        est = read_sync(directory) if sync else None
+        if est is not None:
+            take, music = apply_sync(take, music, est)
+        musics.append(music)
+        sticks.append(take)
     return sticks, musics, labels, dirs
 
 
@@ -295,10 +335,12 @@ class SequenceDataset(Dataset):
     """Pose takes (+ their audio tracks); an item is a random window of `seq_length` seconds (utils.py:48-125).
     `name`: the dataset folder, or with resume=True a dict {'sequences', 'labels', 'dirs'[, 'musics']}.
     `crop_rng` (extension): a numpy RandomState / Generator the window starts are drawn from; default = numpy's global
-    generator, which is what the reference draws from (utils.py:245-248), so seeded runs crop identically."""
+    generator, which is what the reference draws from (utils.py:245-248), so seeded runs crop identically.
+    `sync` (extension): trim the takes that have an accepted sync.json (load_all; the YAML key dataset.sync, off by
+    default)."""
 
     def __init__(self, name, config, resume=False, scaler=None, dance_types=("W", "C", "R", "T"), withaudio=False,
-                 crop_rng=None):
+                 crop_rng=None, sync=False):
         self.aud_rate, self.vid_rate = config["audio_rate"], config["video_rate"]
         self.seq_length, self.feat_size = config["seq_length"], config["feat_size"]
         self.stick_length = int(self.seq_length * self.vid_rate)
@@ -311,7 +353,7 @@ class SequenceDataset(Dataset):
             poses, self.labels, self.dirs = name["sequences"], name["labels"], name["dirs"]
             tracks = name["musics"] if withaudio else None
         else:
-            takes, tracks, letters, self.dirs = load_all(name, list(dance_types))
+            takes, tracks, letters, self.dirs = load_all(name, list(dance_types), sync=sync)
             self.labels = one_hot_encode(letters)
             poses = [t["skeletons"] for t in takes]
         self._poses = _Ragged(poses)
@@ -508,11 +550,36 @@ def make_loaders(dataset, batch_size, withaudio=True, logdir=None, device=None):
 
 
 # --------------------------------------------------------------------------------------- synthetic dataset folder
+def planted_take(frames, samples, hop, lag, stretch=1.0, seed=0):
+    """A take with a known audio-motion offset -> (audio (samples,) fp64, poses (round(frames stretch), 23, 3) fp64):
+    quiet noise with a decaying burst at irregular click frames c (6 to 14 frames apart, at sample c hop + 100), and a
+    body that all but stops at times c + lag (in audio frames), recorded `stretch` times slower: pose frame i shows
+    time i / stretch. The profile of metrics.sync_curves peaks at lag_frames = lag, factor = 1 / stretch."""
+    rng = np.random.default_rng(seed)
+    x = 0.05 * rng.standard_normal(samples)
+    clicks, c = [], 3
+    while c < frames - 2:
+        clicks.append(c)
+        c += int(rng.integers(6, 15))
+    for c in clicks:
+        p = c * hop + 100
+        n = min(3000, samples - p)
+        if n > 0:
+            x[p:p + n] += 0.8 * np.exp(-np.arange(n) / 400.0) * rng.standard_normal(n)
+    n = int(round(frames * stretch))
+    t = np.arange(n) / float(stretch)
+    near = np.exp(-(t[:, None] - np.asarray(clicks, dtype=np.float64)[None, :] - lag) ** 2 / (2.0 * 1.5 ** 2)).sum(axis=1)
+    amp = 0.6 - 0.4 * np.minimum(1.0, near)
+    return x, np.cumsum(amp[:, None, None] / stretch * (1.0 + 0.2 * rng.standard_normal((n, 23, 3))), axis=0)
+
+
 def write_synthetic_dataset(folder, n_takes=8, seconds=8, audio_rate=16000, video_rate=25, seed=0,
-                            styles="CRTW"):
+                            styles="CRTW", planted=None):
     """A folder in the on-disk format the loaders above read (DANCE_<style>_<n>/{skeletons.json | new_skeletons.json,
     config.json, resampled_audio_extract.wav}) filled with random poses / audio: lets the train scripts' dataset
-    path run end to end without the real (absent) Music-to-Dance-Motion-Synthesis data."""
+    path run end to end without the real (absent) Music-to-Dance-Motion-Synthesis data. planted: None, or a list of
+    (lag, stretch) - take n is then planted_take(..., *planted[n % len(planted)]): clicks and a dance that follows them
+    lag frames late (for prepare_data --sync and --waltz-factor auto)."""
     from scipy.io import wavfile
     rng = np.random.RandomState(seed)
     os.makedirs(folder, exist_ok=True)
@@ -523,11 +590,21 @@ def write_synthetic_dataset(folder, n_takes=8, seconds=8, audio_rate=16000, vide
         frames = seconds * video_rate + int(rng.randint(0, video_rate))
         walk = np.cumsum(rng.randn(frames, 23, 3) * 0.02, axis=0) + rng.randn(1, 23, 3)
         center = np.cumsum(rng.randn(frames, 3) * 0.01, axis=0)
+        samples = None
+        if planted is not None:
+            samples = seconds * audio_rate + int(rng.randint(0, audio_rate))
+            lag, stretch = planted[n % len(planted)]
+            track, walk = planted_take(frames, samples, int(audio_rate / video_rate), lag, stretch, seed + n)
+            frames = len(walk)
+            center = np.zeros((frames, 3))
         with open(d + _skeleton_file("DANCE_%s" % style), "w") as f:
             json.dump({"skeletons": walk.tolist(), "center": center.tolist()}, f)
         with open(d + "/config.json", "w") as f:
             json.dump({"start_position": 0, "end_position": frames}, f)
-        samples = seconds * audio_rate + int(rng.randint(0, audio_rate))
-        pcm = np.clip(rng.randn(samples) * 3000.0, -32767, 32767).astype(np.int16)
+        if samples is None:
+            samples = seconds * audio_rate + int(rng.randint(0, audio_rate))
+            pcm = np.clip(rng.randn(samples) * 3000.0, -32767, 32767).astype(np.int16)
+        else:
+            pcm = np.clip(np.rint(track * 8192.0), -32767, 32767).astype(np.int16)
         wavfile.write(d + "/resampled_audio_extract.wav", audio_rate, pcm)
     return folder

@@ -1239,6 +1239,49 @@ class HipKernels:
                 float(sigma_align), _ptr(scores), *[_ptr(t) for t in extra])
         return (scores,) + extra if return_events else scores
 
+    def gauss_smooth(self, c, sigma):
+        """c (B, T) -> g(c, sigma) (B, T): the smoothing of beat_align, bit-equal to its smoothed curves, for rows of
+        any length (m2d_gauss_smooth)"""
+        dev = _chk(c)
+        if c.dim() != 2 or c.shape[0] == 0:
+            raise _lib.M2dError("gauss_smooth: a curve (B, T) expected, got %s" % (tuple(c.shape),))
+        B, T = c.shape
+        out = torch.empty((B, T), dtype=torch.float32, device=dev)
+        _launch("m2d_gauss_smooth", dev, _ptr(c), B, T, float(sigma), _ptr(out))
+        return out
+
+    def sync_scan_max_frames(self):
+        return _lib.lib().m2d_sync_scan_max_frames()
+
+    def sync_scan(self, a, b, factors, max_lag, min_overlap, na=None, nb=None):
+        """a (B, Ta), b (B, Tb) fp32 curves (rows may be cut from wider buffers), na / nb optional int32 (B,) row
+        lengths on the device -> (r (B, F, 2 max_lag + 1) fp64, n (same) int32): the Pearson correlation of a[j] with
+        b at (j + l) / f for every factor f and lag l in [-max_lag, max_lag], and the number of pairs (m2d_sync_scan)"""
+        dev, lda = self._rows2d("sync_scan", a)
+        devb, ldb = self._rows2d("sync_scan", b)
+        B, Ta = a.shape
+        if devb != dev or b.shape[0] != B or B == 0:
+            raise _lib.M2dError("sync_scan: a %s on %s and b %s on %s do not go together"
+                                % (tuple(a.shape), dev, tuple(b.shape), devb))
+        Tb = b.shape[1]
+        limit = self.sync_scan_max_frames()
+        if max(Ta, Tb) > limit:
+            raise _lib.M2dError("sync_scan: %d frames a row, the kernel takes at most %d (scan the take in sections)"
+                                % (max(Ta, Tb), limit))
+        for name, t in (("na", na), ("nb", nb)):
+            if t is not None and (not t.is_cuda or t.device != dev or t.dtype != torch.int32 or not t.is_contiguous()
+                                  or tuple(t.shape) != (B,)):
+                raise _lib.M2dError("sync_scan: %s must be a contiguous int32 tensor (%d,) on %s" % (name, B, dev))
+        fac = [float(f) for f in factors]
+        F, L = len(fac), int(max_lag)
+        if F == 0 or L < 0:
+            raise _lib.M2dError("sync_scan: at least one factor and max_lag >= 0 expected")
+        r = torch.empty((B, F, 2 * L + 1), dtype=torch.float64, device=dev)
+        n = torch.empty((B, F, 2 * L + 1), dtype=torch.int32, device=dev)
+        _launch("m2d_sync_scan", dev, _ptr(a), lda, _ptr(na), _ptr(b), ldb, _ptr(nb), B, Ta, Tb,
+                (ctypes.c_double * F)(*fac), F, L, int(min_overlap), _ptr(r), _ptr(n))
+        return r, n
+
     # ---------------------------------------------------------------- distribution scores (metrics.py)
     @staticmethod
     def _chk64(what, *tensors):

@@ -31,6 +31,13 @@ distances:
     rows        -> k-th nearest-neighbour radii inside a set (m2d_knn_radii)
     rows, radii -> per query: in how many balls it lies, and its nearest row of the other set (m2d_ball_query)
     both        -> prdc(real, fake, k)
+
+Audio-motion synchronisation (include/m2d.h "audio-motion synchronisation") asks where a take's
+dance sits on its music - the reference's takes are not synchronised, and its waltz takes run at another speed:
+
+    audio, poses -> the smoothed onset curve and the negated smoothed speed curve (sync_curves: m2d_gauss_smooth)
+    curves       -> their correlation over time-scale factors and integer lags (sync_profile: m2d_sync_scan)
+    profile      -> factor, lag, peak, second peak (sync_estimate, host fp64)
 """
 import numpy as np
 import torch
@@ -151,6 +158,82 @@ def beat_scores(audio, poses, hop, rate=16000, n_fft=1024, bands=None, gamma=1.0
         raise ValueError("beat_scores: %d audio rows for %d dances" % (x.shape[0], p.shape[0]))
     onset = onset_strength(x, p.shape[1], hop, n_fft, bands, rate, gamma)
     return beat_alignment(onset, motion_speed(p), **kw)
+
+
+# --------------------------------------------------------------------------- audio-motion synchronisation of a take
+def sync_curves(audio, poses, hop, rate=16000, n_fft=1024, bands=None, gamma=1.0, sigma_onset=1.0, sigma_speed=2.0):
+    """The two curves whose correlation places a dance on its music, for one take or a batch of
+    equal-length takes: audio (N,) / (B, N) at `rate` Hz, poses (T, J, 3) / (B, T, J, 3) / (.., T, 3 J), `hop` samples a
+    pose frame -> (a (B, ceil(N / hop)), b (B, T)):
+        a = g(onset_strength(audio), sigma_onset)       peaks on the musical onsets
+        b = -g(motion_speed(poses), sigma_speed)        peaks where the dancer stops (motion events are speed minima)
+    g is the smoothing of beat_alignment (m2d_gauss_smooth). The two lengths differ when audio and poses do."""
+    p = _pose_rows(poses)
+    x = _rows(audio)
+    if x.shape[0] != p.shape[0]:
+        raise ValueError("sync_curves: %d audio rows for %d dances" % (x.shape[0], p.shape[0]))
+    hop = int(hop)
+    K = kernels.impl()
+    a = K.gauss_smooth(onset_strength(x, -(-x.shape[1] // hop), hop, n_fft, bands, rate, gamma), sigma_onset)
+    return a, -K.gauss_smooth(motion_speed(p), sigma_speed)
+
+
+def _row_lengths(n, rows, device):
+    if n is None:
+        return None
+    t = torch.as_tensor(n).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+    if t.numel() != rows:
+        raise ValueError("sync_profile: %d lengths for %d rows" % (t.numel(), rows))
+    return t
+
+
+def sync_profile(a, b, factors=(1.0,), max_lag=250, min_overlap=64, na=None, nb=None):
+    """a (B, Ta), b (B, Tb) fp32 curves on the device (one row: (Ta,), (Tb,)), na / nb optional per-row lengths ->
+    (r (B, F, 2 max_lag + 1) fp64, n int32): r[., i, l + max_lag] is the Pearson correlation of a[j] with b read at
+    (j + l) / factors[i] (linear interpolation), over the n pairs whose position lies in b; NaN where n < min_overlap
+    or a variance is zero. l > 0: the motion lags the audio by l frames; a factor f is what retime_sequence would be
+    given (new length round(Tb f)). One m2d_sync_scan launch for the whole batch."""
+    a, b = _rows(a), _rows(b)
+    return kernels.impl().sync_scan(a, b, factors, int(max_lag), int(min_overlap),
+                                    _row_lengths(na, a.shape[0], a.device), _row_lengths(nb, a.shape[0], a.device))
+
+
+SYNC_WINDOW = 3   # r_second looks outside |l - l*| <= SYNC_WINDOW
+
+
+def sync_estimate(r, n, factors, max_lag):
+    """The profile of sync_profile -> one dict per row: 'factor' and 'lag_frames' = the (f*, l*) of the largest non-NaN
+    r (ties: the smallest |l|, then the first factor), 'r' its value, 'overlap' its n, 'r_second' the largest r of the
+    same factor outside |l - l*| <= 3, 'lag' the parabolic sub-frame refinement through l* - 1, l*, l* + 1 (= l* at the
+    grid's edge, next to a NaN, or on a flat top; reported only - what is applied is lag_frames). A row without any
+    defined r, or a missing r_second, gives None. Host fp64 on the copied profile."""
+    R = np.asarray(torch.as_tensor(r).detach().cpu().numpy(), dtype=np.float64)
+    N = np.asarray(torch.as_tensor(n).detach().cpu().numpy())
+    L = int(max_lag)
+    factors = [float(f) for f in factors]
+    if R.ndim != 3 or R.shape[1:] != (len(factors), 2 * L + 1) or N.shape != R.shape:
+        raise ValueError("sync_estimate: r and n (B, %d, %d) expected, got %s and %s"
+                         % (len(factors), 2 * L + 1, R.shape, N.shape))
+    lags = np.arange(-L, L + 1)
+    out = []
+    for row, cnt in zip(R, N):
+        ok = ~np.isnan(row)
+        if not ok.any():
+            out.append({"factor": None, "lag_frames": None, "lag": None, "r": None, "r_second": None, "overlap": 0})
+            continue
+        top = row[ok].max()
+        cand = [(abs(int(lags[k])), i, k) for i, k in zip(*np.nonzero(ok & (row == top)))]
+        _, i, k = min(cand)
+        prof = row[i]
+        lag = float(lags[k])
+        if 0 < k < 2 * L and not np.isnan(prof[k - 1]) and not np.isnan(prof[k + 1]):
+            den = prof[k - 1] - 2.0 * prof[k] + prof[k + 1]
+            if den != 0.0:
+                lag += 0.5 * (prof[k - 1] - prof[k + 1]) / den
+        rest = prof[(np.abs(lags - lags[k]) > SYNC_WINDOW) & ~np.isnan(prof)]
+        out.append({"factor": factors[i], "lag_frames": int(lags[k]), "lag": lag, "r": float(top),
+                    "r_second": float(rest.max()) if rest.size else None, "overlap": int(cnt[i, k])})
+    return out
 
 
 # ------------------------------------------------------------------------------------------- distribution scores

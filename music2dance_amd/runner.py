@@ -249,7 +249,7 @@ def sequence_dataset(run, withaudio):
     print("Loading sticks and sequences datasets...")
     sticks = D.StickDataset(folder, normalize="minmax")
     return D.SequenceDataset(folder, run.cfg["dataset"], dance_types=run.cfg["dance_types"], scaler=sticks.scaler,
-                             withaudio=withaudio)
+                             withaudio=withaudio, sync=run.cfg["dataset"].get("sync", False))
 
 
 def pose_sequence_loader(run, batch_size):

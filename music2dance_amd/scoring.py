@@ -101,7 +101,7 @@ def validation_takes(opts, cfg, withaudio=True):
     folder = runner.dataset_folder(cfg, opts.folder)
     scaler = D.StickDataset(folder, normalize="minmax").scaler
     dataset = D.SequenceDataset(folder, cfg["dataset"], dance_types=cfg["dance_types"], scaler=scaler,
-                                withaudio=withaudio)
+                                withaudio=withaudio, sync=cfg["dataset"].get("sync", False))
     where = {d: i for i, d in enumerate(dataset.dirs)}
     missing = [d for d in val_dirs if d not in where]
     if missing:
