@@ -1770,10 +1770,28 @@ static double rounds_cost(const RoundsModel& m, int b, long long W, double cps, 
   return 6.0 + tot;
 }
 
+// the rounds model of a plan kind, or NULL (the general model prices the launch)
+static const RoundsModel* plan_rounds_model(int kind) {
+  static const bool rounds_on = m2d_env_on("M2D_PLAN_ROUNDS");
+  return !rounds_on ? nullptr : kind == M2D_PLAN_BWD_WEIGHT ? &kRoundsBwdW : kind == M2D_PLAN_BWD_DATA ? &kRoundsBwdD : nullptr;
+}
+
+// THE envelope of split factors: the largest one a plan of this query may have, 1 where K is not split (no split allowed,
+// a phased backward-data launch, fewer than 8 chunks). Every split keeps 4 chunks at least; 128 splits at most, 256 under
+// model 5 and the rounds model. plan_candidates clamps its candidates to it, a forced plan (m2d_debug_force_plan) is
+// refused beyond it.
+static long long plan_max_splits(int nchunks, int phases, bool allow_split, int kind) {
+  if (!allow_split || phases > 1 || nchunks < 8) return 1;
+  const bool model5 = g_plan_model.load(std::memory_order_relaxed) == 5;
+  const long long max_splits = (model5 || plan_rounds_model(kind)) ? 256 : 128;
+  return max_splits < nchunks / 4 ? max_splits : nchunks / 4;
+}
+static inline bool plan_bm_ok(int bm, bool k4) { return bm == 128 || bm == 64 || (bm == 32 && !k4); }
+
 static int plan_candidates(int M, int N, int nchunks, int phases, bool allow_split, double small_tile_penalty,
                            PlanCand* out, int kind = 0) {
   const int ph = phases > 1 ? phases : 1;
-  const bool can_split = allow_split && phases <= 1;
+  const long long sp_max = plan_max_splits(nchunks, phases, allow_split, kind);
   const long long nt = m2d_ceil_div(N, 128);
   const int bms[3] = {128, 64, 32};
   // us per block-chunk with the matrix pipes busy; `small_tile_penalty` (>= 1) prices operands whose
@@ -1797,9 +1815,7 @@ static int plan_candidates(int M, int N, int nchunks, int phases, bool allow_spl
   const bool model5 = g_plan_model.load(std::memory_order_relaxed) == 5;
   static const double slab_mul = m2d_env_double("M2D_SLAB_COST", 1.0);   // A/B lever
   const double lchunk[3] = {1.50, 1.35, 1.20};
-  static const bool rounds_on = m2d_env_on("M2D_PLAN_ROUNDS");
-  const RoundsModel* rm = !rounds_on ? nullptr : kind == M2D_PLAN_BWD_WEIGHT ? &kRoundsBwdW : kind == M2D_PLAN_BWD_DATA ? &kRoundsBwdD : nullptr;
-  const long long max_splits = (model5 || rm) ? 256 : 128;
+  const RoundsModel* rm = plan_rounds_model(kind);
   PlanCand all[40];
   int na = 0;
   for (int b = 0; b < 3; ++b) {
@@ -1807,11 +1823,10 @@ static int plan_candidates(int M, int N, int nchunks, int phases, bool allow_spl
     long long cand[10];
     int nc = 0;
     cand[nc++] = 1;
-    if (can_split && nchunks >= 8) {
+    if (sp_max > 1) {
       for (int k = 1; k <= 8; ++k) {
         long long sp = (256LL * k) / tiles;
-        if (sp > max_splits) sp = max_splits;
-        if (sp > nchunks / 4) sp = nchunks / 4;
+        if (sp > sp_max) sp = sp_max;
         if (sp > 1) cand[nc++] = sp;
       }
     }
@@ -1868,6 +1883,22 @@ extern "C" int m2d_debug_last_plan(int* out) {
 }
 #endif
 
+// test-only (tests/plan_cases.py binds it with ctypes; not part of include/m2d.h): every launch of the process takes the
+// plan (bm, splits) instead of the model's first feasible candidate, until (0, 0) clears it - so the suite can run each
+// tile height and split form on shapes of its choosing. select_plan honours it only inside the envelope the model itself
+// can emit for the query and refuses the launch otherwise; whether a split runs in one launch stays decide_fused's
+// decision. The size queries (m2d_gemm_plan) cover its slab. Process-global, cleared by default.
+static std::atomic<int> g_forced_plan{0};   // bm << 16 | splits; 0 = none
+extern "C" int m2d_debug_force_plan(int bm, int splits) {
+  if (bm == 0 && splits == 0) {
+    g_forced_plan.store(0, std::memory_order_relaxed);
+    return M2D_OK;
+  }
+  if (!plan_bm_ok(bm, false) || splits < 1 || splits > 256) M2D_FAIL(M2D_ERR_ARG, "m2d_debug_force_plan: bm 32 / 64 / 128, 1 to 256 splits");
+  g_forced_plan.store(bm << 16 | splits, std::memory_order_relaxed);
+  return M2D_OK;
+}
+
 // The model's first choice; ws_bytes covers every candidate the launcher may pick.
 M2dGemmPlan m2d_gemm_plan(int M, int N, int nchunks, int phases, bool allow_split, double small_tile_penalty, int kind) {
   PlanCand c[M2D_MAX_CAND];
@@ -1878,6 +1909,11 @@ M2dGemmPlan m2d_gemm_plan(int M, int N, int nchunks, int phases, bool allow_spli
   pl.ws_bytes = 0;
   for (int i = 0; i < n; ++i) {
     const size_t b = m2d_slab_bytes(M, N, c[i].bm, c[i].splits);
+    if (b > pl.ws_bytes) pl.ws_bytes = b;
+  }
+  if (const int f = g_forced_plan.load(std::memory_order_relaxed)) {   // the slab of a forced plan this query admits
+    const int splits = f & 0xffff;
+    const size_t b = splits <= plan_max_splits(nchunks, phases, allow_split, kind) ? m2d_slab_bytes(M, N, f >> 16, splits) : 0;
     if (b > pl.ws_bytes) pl.ws_bytes = b;
   }
 #ifdef M2D_TUNING
@@ -2034,6 +2070,27 @@ static int select_plan(const M2dGemmParams& p, const PlanQuery& q, Plan* out) {
   const bool stats = p.O.row_part != nullptr;
   const bool allow_split = q.allow_split && !(stats && !stats_split_enabled());
   const size_t mn4 = (size_t)p.M * (size_t)p.N * sizeof(float);
+  if (const int f = g_forced_plan.load(std::memory_order_relaxed)) {
+    // a forced plan (m2d_debug_force_plan): taken as it is where the model could emit it for this query, refused where
+    // not - never adjusted, and nothing has been launched yet
+    const int bm = f >> 16, splits = f & 0xffff;
+    if (p.tall_last_rb ? (bm != 128 || splits != 1) : !plan_bm_ok(bm, q.k4))
+      M2D_FAIL(M2D_ERR_ARG, "%s: forced plan %d x %d: this launch has no %d-row tile", q.what, bm, splits, bm);
+    unsigned* t = nullptr;
+    if (splits > 1) {
+      const long long sp_max = plan_max_splits(q.nchunks, q.phases, allow_split, q.kind);
+      if (splits > sp_max)
+        M2D_FAIL(M2D_ERR_ARG, "%s: forced plan %d x %d: %lld splits at most (%d chunks)", q.what, bm, splits, sp_max, q.nchunks);
+      const size_t need = m2d_slab_bytes(p.M, p.N, bm, splits);
+      if (!q.ws || q.ws_bytes < need)
+        M2D_FAIL(M2D_ERR_WORKSPACE, "%s: forced plan %d x %d needs %zu workspace bytes, got %zu", q.what, bm, splits, need, q.ws_bytes);
+      t = decide_fused(p, q, bm, splits);
+      if (stats && !t)
+        M2D_FAIL(M2D_ERR_ARG, "%s: forced plan %d x %d: epilogue statistics need split-K in one launch", q.what, bm, splits);
+    }
+    *out = {bm, splits, t};
+    return M2D_OK;
+  }
   PlanCand cand[M2D_MAX_CAND];
   int nc = 0;
   auto first_feasible = [&](bool split) {

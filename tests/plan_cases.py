@@ -19,9 +19,10 @@ The workspace of a row is what the library's own m2d_conv1d_workspace_bytes asks
 partials, which the conv entry point takes off the front before it calls the launcher), the tickets are the 64 KB every
 stream gets (kernels._TICKET_WORDS), the workspace is 16-byte aligned.
 """
+import contextlib
 import ctypes
 
-from music2dance_amd import _lib
+from music2dance_amd import _lib, kernels
 from music2dance_amd.kernels import _TICKET_WORDS
 
 GENERAL, K4 = 0, 1          # m2d_gemm_launch, m2d_conv_k4_launch
@@ -39,7 +40,43 @@ def _handle():
         _h.m2d_debug_select_plan.argtypes = [i, i, i, i, i, i, ctypes.c_double, i, i, i, z, i, z, i, ctypes.POINTER(i)]
         _h.m2d_conv1d_workspace_bytes.restype = z
         _h.m2d_conv1d_workspace_bytes.argtypes = [i] * 8
+        _h.m2d_gemm_workspace_bytes.restype = z
+        _h.m2d_gemm_workspace_bytes.argtypes = [i] * 4
+        _h.m2d_debug_force_plan.restype = i
+        _h.m2d_debug_force_plan.argtypes = [i, i]
     return _h
+
+
+def force_plan(bm, splits):
+    """csrc/gemm_engine.hip: m2d_debug_force_plan -> rc. (0, 0) clears. The binding's cached workspace sizes follow the
+    plans (kernels._ws_bytes): dropped with every change."""
+    kernels._WS_BYTES.clear()
+    return _handle().m2d_debug_force_plan(bm, splits)
+
+
+@contextlib.contextmanager
+def forced_plan(bm, splits):
+    """Every engine launch inside the scope takes the plan (bm, splits) or is refused (M2dError); cleared on the way out."""
+    try:
+        rc = force_plan(bm, splits)
+        assert rc == 0, (bm, splits, rc)
+        yield
+    finally:
+        force_plan(0, 0)
+
+
+def gemm_ws_bytes(mode, M, N, K):
+    """include/m2d.h: m2d_gemm_workspace_bytes, uncached"""
+    return _handle().m2d_gemm_workspace_bytes(mode, M, N, K)
+
+
+def max_splits(nchunks, phases, allow_split, plan_kind):
+    """The largest split factor a plan of this query may have under the default cost model (written out from DESIGN.md's
+    plan-selection rules, not read from the library): 4 chunks per split at least, 128 splits (256 for the rounds-model
+    kinds 1 and 2) at most, none for phased launches and under 8 chunks."""
+    if not allow_split or phases > 1 or nchunks < 8:
+        return 1
+    return min(256 if plan_kind in (1, 2) else 128, nchunks // 4)
 
 
 def select_plan(launcher, M, N, nchunks, phases, allow_split, penalty, plan_kind, bwd_data, stats, ws_bytes, ws_aligned,

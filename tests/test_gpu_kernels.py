@@ -279,6 +279,77 @@ def test_gemm_tn_long_k():
     assert rel_err(c, a.double().t() @ b.double()) < 3e-5
 
 
+def _dense_plan(M, N, Kd, with_tickets=True):
+    """(rc, bm, splits, fused): the plan m2d_gemm takes for the shape, asked of the library's own selection (m2d_gemm asks
+    with ceil(K / 16) chunks, no small-tile penalty, the general model and the workspace its size query returns) - so a
+    retuned cost model fails the cases below instead of quietly moving them to another kernel."""
+    from tests import plan_cases as C
+    return C.select_plan(C.GENERAL, M, N, -(-Kd // 16), 1, 1, 0.0, 0, 0, 0, C.gemm_ws_bytes(0, M, N, Kd), True,
+                         C.TICKET_BYTES if with_tickets else 0)
+
+
+def _gemm_three_modes(M, N, Kd, seed, **epilogue):
+    """a (M, K), b^T (N, K): the product through modes 0, 1 and 2 -> the three outputs and the fp64 product"""
+    a = gen(M, Kd, seed=seed)
+    bt = gen(N, Kd, seed=seed + 1, scale=1.0 / math.sqrt(max(Kd, 1)))
+    ad, btd = a.to(DEV), bt.to(DEV)
+    b, at = btd.t().contiguous(), ad.t().contiguous()
+    outs = [K().gemm(0, ad, btd, **epilogue), K().gemm(1, ad, b, **epilogue), K().gemm(2, at, b, **epilogue)]
+    return outs, a.double() @ bt.double().t()
+
+
+def test_gemm_gru_input_projection_takes_the_64_row_tile():
+    """The GRU input projection at the benchmark's size, bias + ReLU, in the three modes (kernel families)."""
+    M, N, Kd = 7680, 720, 250
+    assert _dense_plan(M, N, Kd) == (0, 64, 1, 0)
+    bias = gen(N, seed=3)
+    outs, prod = _gemm_three_modes(M, N, Kd, 1, bias=bias.to(DEV), act=1)
+    want = (prod + bias.double()).clamp_min(0)
+    for mode, c in enumerate(outs):
+        assert rel_err(c, want) < 2e-5, mode
+
+
+def test_gemm_single_chunk_on_128_row_tiles():
+    M, N, Kd = 512, 15360, 16
+    assert _dense_plan(M, N, Kd) == (0, 128, 1, 0)
+    outs, prod = _gemm_three_modes(M, N, Kd, 4)
+    for mode, c in enumerate(outs):
+        assert rel_err(c, prod) < 2e-5, mode
+
+
+def test_gemm_split_k_with_empty_trailing_splits():
+    """25 chunks in 6 one-launch splits of 5 (the sixth is empty) and 257 chunks in 64 two-launch splits of 5 (twelve are
+    empty), the latter with bias + ReLU + out_mask applied by the reduction kernel."""
+    from music2dance_amd import kernels
+    M, N = 37, 100
+    kernels._stream(torch.device(DEV))   # (registers the stream's tickets)
+    assert _dense_plan(M, N, 400) == (0, 32, 6, 1) and 5 * -(-25 // 6) >= 25
+    outs, prod = _gemm_three_modes(M, N, 400, 5)
+    for mode, c in enumerate(outs):
+        assert rel_err(c, prod) < 2e-5, mode
+    assert _dense_plan(M, N, 4100) == (0, 32, 64, 0) and -(-257 // 5) == 64 - 12
+    bias, om = gen(N, seed=8), gen(M, N, seed=9)
+    outs, prod = _gemm_three_modes(M, N, 4100, 6, bias=bias.to(DEV), act=1, out_mask=om.to(DEV), out_mask_slope=0.2)
+    want = (prod + bias.double()).clamp_min(0) * torch.where(om.double() > 0, 1.0, 0.2)
+    for mode, c in enumerate(outs):
+        assert rel_err(c, want) < 2e-5, mode
+
+
+@pytest.mark.parametrize("Kd", [0, 1, 15, 16, 17])
+def test_gemm_short_contractions(Kd):
+    """K below, at and just above the 16-deep chunk, and none at all: the epilogue alone, act(bias)."""
+    M, N = 33, 69
+    assert _dense_plan(M, N, Kd) == (0, 32, 1, 0)
+    bias = gen(N, seed=3)
+    for act, slope, f in ((1, 0.0, lambda v: v.clamp_min(0)), (2, 0.2, lambda v: torch.where(v < 0, 0.2 * v, v))):
+        outs, prod = _gemm_three_modes(M, N, Kd, 7, bias=bias.to(DEV), act=act, slope=slope)
+        want = f(prod + bias.double())
+        if Kd == 0:
+            assert torch.equal(want, f(bias.double()).expand(M, N))
+        for mode, c in enumerate(outs):
+            assert rel_err(c, want) < 2e-5, (mode, act)
+
+
 BN_CASES = [(64, 128, 1), (7680, 256, 1), (48, 32, 64), (48, 1024, 2), (24, 64, 193), (24, 128, 43), (24, 256, 5),
             (6, 32, 800), (6, 128, 25), (5, 3, 7)]
 
