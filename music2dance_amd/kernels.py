@@ -379,8 +379,9 @@ class HipKernels:
         return ok
 
     @staticmethod
-    def _thin(Cin, ks, stride):
-        return Cin == 1 and ks == 25 and stride == 4
+    def _thin(Cin, Cout, ks, stride):
+        """the library's thin_ok (csrc/conv1d_thin.hip): the single-channel k25 / s4 kernels take 32 output channels only"""
+        return Cin == 1 and Cout == 32 and ks == 25 and stride == 4
 
     def conv1d_fwd(self, x, w, bias, stride, pad, act=0, slope=0.0, residual=None, out_mask=None,
                    out_mask_slope=0.0, with_stats=False, out=None, sum_out=None):
@@ -439,9 +440,9 @@ class HipKernels:
             wp = self.packed_weights(w)[1]
         else:
             full_length = Lout == 1 and pad == 0 and L == ks
-            if (out_mask is not None or residual is not None) and self._thin(Cin, ks, stride):
-                raise _lib.M2dError("conv1d_bwd_data: out_mask / residual are not supported on the thin (Cin = 1, k25 s4) path")
-            wp = None if (full_length or self._thin(Cin, ks, stride)) else self.packed_weights(w)[1]
+            if (out_mask is not None or residual is not None) and self._thin(Cin, Cout, ks, stride):
+                raise _lib.M2dError("conv1d_bwd_data: out_mask / residual are not supported on the thin (Cin = 1, Cout = 32, k25 s4) path")
+            wp = None if (full_length or self._thin(Cin, Cout, ks, stride)) else self.packed_weights(w)[1]
         ws, nws = _workspace(dev, 'm2d_conv1d_workspace_bytes', 1, B, Cin, L, Cout, ks, stride, pad)
         if shared_mask:
             _launch("m2d_conv1d_bwd_data_shared_mask", dev, _ptr(dy), _ptr(w), _ptr(wp), _ptr(dx), B, Cin, L, Cout, ks,
@@ -476,7 +477,7 @@ class HipKernels:
         # 4 800 x 200 positions: 768 + 1 columns ran 7 tiles for 6.008, 2.46 ms at 77 TFLOP/s; the sum pass costs 0.12 ms)
         sep_bias = (with_bias and self._SEPARATE_BIAS and (Cin * ks) % 128 == 0 and
                     (Lout < 16 or Cin * ks <= 512 or (Cin * ks <= 1024 and B * Lout >= 200000))
-                    and not self._thin(Cin, ks, stride) and _bn_scratch(dev, Cout) is not None)
+                    and not self._thin(Cin, Cout, ks, stride) and _bn_scratch(dev, Cout) is not None)
         db = torch.empty((Cout,), dtype=torch.float32, device=dev) if (with_bias and not sep_bias) else None
         ws, nws = _workspace(dev, 'm2d_conv1d_workspace_bytes', 2, B, Cin, L, Cout, ks, stride, pad)
         if bias_from_sample:
