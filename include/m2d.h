@@ -21,6 +21,16 @@
  *     or the result by (mask > 0 ? 1 : mask_slope) — the derivative of the fused
  *     activation — which closes the op set under differentiation for the gradient
  *     penalty's double backward (losses.py:40-44).
+ *   - operand alignment ("Operand alignment"): every float operand needs its natural 4-byte alignment
+ *     and no more (int64 labels 8 bytes, bytes none), unless the entry's comment says otherwise - today the STFT basis
+ *     image, the JPEG workspace, m2d_maxpool2_fwd_from's sample starts and m2d_sync_scan's `r`; an `out` / `sum_out`
+ *     view one float into a buffer is as good as a fresh allocation. Inside the library:
+ *       . plain global loads and stores (to or from registers) may be issued 16 bytes wide at 4-byte alignment - the
+ *         sub-pixel backward-data epilogue does so in every training step (its addresses are 4 q - pad);
+ *       . LDS-DMA wider than 4 bytes, and anything that derives an LDS address or bank layout from a global
+ *         address, is selected only when the source pointer and every row start are 16-byte aligned; the routing
+ *         tests the pointers and takes a narrower kernel otherwise (a direct call of a kernel-specific entry point
+ *         such as m2d_conv1d_fwd_k4 fails with M2D_ERR_ARG instead: it has no other kernel to take).
  */
 #ifndef M2D_H
 #define M2D_H
@@ -106,7 +116,10 @@ int m2d_conv1d_fwd_sum(const float* x, const float* w, const float* w_packed, co
  * is private to the pack / forward pair - k25 / pad 11 layers walk the full groups first and the partial first / last
  * groups of four channels together, so that the zero slots are never multiplied). Same results as
  * m2d_conv1d_fwd up to summation order; m2d_conv1d_k4_applicable says whether a layer qualifies (stride 4,
- * L % 4 == 0, Cin % 4 == 0, Cin >= 16, Cout >= 64). sum_out: optional second output as in m2d_conv1d_fwd_sum. */
+ * L % 4 == 0, Cin % 4 == 0, Cin >= 16, Cout >= 64) BY ITS SHAPE; the pointers are the caller's to test: x and w_k4
+ * must be 16-byte aligned (the 16-byte LDS-DMA reads them; with L % 4 == 0 every row of x then is) - m2d_conv1d_fwd_k4
+ * fails with M2D_ERR_ARG before it launches otherwise, and m2d_conv1d_fwd serves such an x.
+ * sum_out: optional second output as in m2d_conv1d_fwd_sum. */
 int m2d_conv1d_k4_applicable(int Cin, int L, int Cout, int ks, int stride, int pad);
 size_t m2d_conv1d_k4_packed_elems(int Cout, int Cin, int ks, int pad);
 int m2d_conv1d_pack_weights_k4(const float* w, float* out, int Cout, int Cin, int ks, int pad, void* stream);

@@ -606,12 +606,16 @@ __global__ void __launch_bounds__(256) m2d_bn_upsample2_rows_kernel(const BnAppl
 static int launch_apply(BnApplyArgs& a, int B, hipStream_t stream) {
   if (a.out_pitch <= 0) a.out_pitch = a.row_len;
   if (a.out_pitch < a.row_len) M2D_FAIL(M2D_ERR_ARG, "BatchNorm apply: output batch stride smaller than a sample");
-  // (vector stores: the output's sample starts must keep the vector alignment too)
-  const bool vec4 = (a.row_len % 4 == 0) && (a.L == 1 || a.L % 4 == 0) && (a.out_pitch % 4 == 0) && (((uintptr_t)a.out & 15) == 0);
+  // (vector stores: the output's sample starts must keep the vector alignment too. The pointer test covers `out` alone:
+  // x / dy / residual are plain global loads, which need a float's alignment only - include/m2d.h, operand alignment.
+  // With the pooled output in the same pass there is no one-element form - a thread needs both members of a pair - so
+  // that form picks its width by shape and its stores to an `out` off the boundary are plain global ones as well.)
+  const bool fits16 = a.pool_out || ((uintptr_t)a.out & 15) == 0, fits8 = a.pool_out || ((uintptr_t)a.out & 7) == 0;
+  const bool vec4 = (a.row_len % 4 == 0) && (a.L == 1 || a.L % 4 == 0) && (a.out_pitch % 4 == 0) && fits16;
   const bool vec2 = !vec4 && (a.row_len % 2 == 0) && (a.L == 1 || a.L % 2 == 0) && (a.out_pitch % 2 == 0) &&
-                    (((uintptr_t)a.out & 7) == 0);  // e.g. the WaveGAN encoder's L = 794
+                    fits8;  // e.g. the WaveGAN encoder's L = 794
   if (a.pool_out && ((a.L & 1) || !(vec4 || vec2) || a.backward))
-    M2D_FAIL(M2D_ERR_ARG, "BatchNorm apply + max-pool: even L and 8-byte aligned rows");
+    M2D_FAIL(M2D_ERR_ARG, "BatchNorm apply + max-pool: even L and an even output batch stride");
   const int rvl = vec4 ? a.row_len / 4 : vec2 ? a.row_len / 2 : a.row_len;
   unsigned gx, gy;
   if (rvl >= 256) {
@@ -830,10 +834,12 @@ int m2d_bn_fwd_sums_upsample2_to(const float* x, const double* sums, double coun
   hipStream_t stream = (hipStream_t)stream_;
   const long long per = (long long)C * L;
   if (up_batch_stride <= 0) up_batch_stride = 2 * per;
-  const bool misfit = (per & 1) || up_batch_stride < 2 * per || (up_batch_stride & 3) || (((uintptr_t)x | (uintptr_t)up) & 15u);
+  // (shape only: the 8-byte loads of x and the 16-byte stores of up are plain global accesses, good at a float's alignment
+  // - include/m2d.h, operand alignment; the sample pitch keeps the vectors of every sample on the first one's phase)
+  const bool misfit = (per & 1) || up_batch_stride < 2 * per || (up_batch_stride & 3);
   const bool rows = (L & 1) == 0;   // (the flat form reads the parameters per pair: it keeps the arrays)
   BnApplyArgs a;
-  if (int rc = bn_fwd_sums_begin("m2d_bn_fwd_sums_upsample2_to", misfit ? "C * L even, 16-byte aligned samples" : nullptr,
+  if (int rc = bn_fwd_sums_begin("m2d_bn_fwd_sums_upsample2_to", misfit ? "C * L even, batch stride a multiple of 4" : nullptr,
                                  rows, x, sums, count, gamma, beta, running_mean, running_var, up, save_mean, save_invstd,
                                  B, C, L, eps, momentum, act, slope, stream, a))
     return rc;

@@ -20,6 +20,10 @@ static inline int conv_out_len(int L, int ks, int stride, int pad) {
 }
 
 static inline bool fits_i32(long long v) { return v >= 0 && v < 2147483647LL; }
+// every listed pointer sits on a 16-byte boundary (absent ones, NULL, count as aligned): what the routing asks before it
+// hands operands to a kernel whose accesses need more than a float's alignment (include/m2d.h: operand alignment)
+template <class... P>
+static inline bool al16(const P*... p) { return ((0u | ... | (uintptr_t)p) & 15u) == 0; }
 
 // Forward conv as a GEMM. Cin >= 16: K ordered (tap, channel) - hi = tap, lo = ci - over the
 // packed weights wp (Cout, ks, Cin): every 16-chunk sits on one tap, so the padding window is
@@ -244,7 +248,11 @@ static int conv1d_fwd_impl(const float* x, const float* w, const float* w_packed
   }
   if (!wv && !stats) {
     // the pose critic's TemporalBlock convolutions (stride 1, "same" padding, 128 output channels): csrc/tcn.hip
-    const int nt = m2d_tcn_conv_tile(B, Cin, L, Cout, ks, stride, pad);
+    // (its epilogue moves 16-byte pieces of out / out_mask / residual / sum_out and its weight stream is a 16-byte
+    // LDS-DMA: an operand off 16 bytes - an `out` view into a wider buffer - goes through the engine below, whose
+    // workspace m2d_conv1d_workspace_bytes sizes for every shape. x is staged 4 bytes a lane: any alignment.)
+    const bool al = al16(y, out_mask, residual, sum_out, w_packed);
+    const int nt = al ? m2d_tcn_conv_tile(B, Cin, L, Cout, ks, stride, pad) : 0;
     if (nt > 0) {
       M2dTcnConv t;
       memset(&t, 0, sizeof(t));
@@ -390,6 +398,8 @@ int m2d_conv1d_fwd_k4(const float* x, const float* w_k4, const float* bias, floa
   if (!m2d_conv1d_k4_applicable(Cin, L, Cout, ks, stride, pad))
     M2D_FAIL(M2D_ERR_ARG, "m2d_conv1d_fwd_k4: layer not eligible (stride 4, L %% 4 == 0, Cin %% 4 == 0, Cin >= 16, Cout >= 64)");
   if (B <= 0 || !x || !w_k4 || !y) M2D_FAIL(M2D_ERR_ARG, "m2d_conv1d_fwd_k4: bad arguments");
+  // (both operands go to the LDS 16 bytes a lane; m2d_conv1d_k4_applicable sees the shape only - the caller tests the pointers)
+  if (!al16(x, w_k4)) M2D_FAIL(M2D_ERR_ARG, "m2d_conv1d_fwd_k4: x and the packed image must be 16-byte aligned (m2d_conv1d_fwd takes any x)");
   if (sum_out && !residual) M2D_FAIL(M2D_ERR_ARG, "m2d_conv1d_fwd_k4: sum_out needs a residual");
   const int Lout = conv_out_len(L, ks, stride, pad);
   if (!fits_i32((long long)B * Cin * L) || !fits_i32((long long)B * Cout * Lout))
@@ -608,7 +618,8 @@ static int conv1d_bwd_data_impl(const float* dy, const float* w, const float* w_
   if (stride == 1 && Lout == L && (mask_wrap % 4u) == 0) {
     // dx[n, ci, j] = sum_{t', co} wb[co, ks - 1 - t', ci] dy[n, co, j - pad + t']: the "same" convolution of dy with the
     // flipped taps of the (Cout, ks, Cin) image - the TemporalBlock kernel with the roles of the channels swapped
-    const int nt = m2d_tcn_conv_tile(B, Cout, L, Cin, ks, stride, pad);
+    // (dy and its mask are staged 4 bytes a lane; the 16-byte accesses are the epilogue's and the weight stream's)
+    const int nt = al16(dx, out_mask, residual, w_packed) ? m2d_tcn_conv_tile(B, Cout, L, Cin, ks, stride, pad) : 0;
     if (nt > 0) {
       M2dTcnConv t;
       memset(&t, 0, sizeof(t));
@@ -766,8 +777,10 @@ static int conv1d_bwd_weight_impl(const float* x, const float* dy, float* dw, fl
                                ws_bytes, wv, (hipStream_t)stream);
   if (wv && (Cin != 1 || Lout < M2D_BK))
     M2D_FAIL(M2D_ERR_ARG, "m2d_conv1d_bwd_weight_windows: single-channel convs with >= %d output positions only", M2D_BK);
-  if (!wv && Lout == L && m2d_tcn_wgrad_applicable(B, Cin, L, Cout, ks, stride, pad)) {
-    // the pose critic's TemporalBlock convolutions: csrc/tcn.hip
+  if (!wv && Lout == L && al16(dy, dy_mask) && m2d_tcn_wgrad_applicable(B, Cin, L, Cout, ks, stride, pad)) {
+    // the pose critic's TemporalBlock convolutions: csrc/tcn.hip (16-byte buffer loads of dy / dy_mask whose LDS image
+    // follows the piece index; x is read 4 bytes a lane. Off 16 bytes: the engine below - the workspace query takes
+    // the larger of the two sizes)
     M2dTcnWgrad t;
     memset(&t, 0, sizeof(t));
     t.x = x;

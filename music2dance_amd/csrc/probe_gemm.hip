@@ -109,6 +109,9 @@ int m2d_debug_probe_gemm(const float* a, const float* b, float* c, int M, int N,
   if (M <= 0 || N <= 0 || K <= 0 || M % 128 || N % 128 || K % 16 || (size_t)M * K * 4 >= 0x80000000ull ||
       (size_t)N * K * 4 >= 0x80000000ull)
     M2D_FAIL(M2D_ERR_ARG, "m2d_debug_probe_gemm: M, N multiples of 128, K of 16, operands below 2 GiB");
+  // (both operands go to the LDS 16 bytes a lane, C leaves in 8-byte stores: include/m2d.h, operand alignment)
+  if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u)
+    M2D_FAIL(M2D_ERR_ARG, "m2d_debug_probe_gemm: a, b and c must be 16-byte aligned");
   hipLaunchKernelGGL(m2d_probe_gemm_kernel, dim3((M / 128) * (N / 128)), dim3(256), 0, (hipStream_t)stream, a, b, c, M, N, K);
   M2D_CHECK_LAUNCH("m2d_probe_gemm_kernel");
   return M2D_OK;

@@ -401,7 +401,8 @@ class HipKernels:
         if sum_out is not None:
             assert not with_stats and residual is not None and tuple(sum_out.shape) == tuple(y.shape)
         # tap-vectorised stride-4 forward (audio critic l2..l5 and the penalty's tangent through them), or the engine
-        k4 = self._k4(Cin, L, Cout, ks, stride, pad)
+        # (the k4 kernel stages x by 16-byte LDS-DMA: an x off 16 bytes - a view into a wider buffer - takes the engine)
+        k4 = self._k4(Cin, L, Cout, ks, stride, pad) and x.data_ptr() % 16 == 0
         if k4:
             wk4 = self.packed_k4(w, pad)
         else:
