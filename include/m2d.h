@@ -478,6 +478,45 @@ int m2d_jpeg_encode(const unsigned char* frames, long n_frames, int height, int 
 int m2d_resample_poly(const float* x, long long x0, int nx, long long ldx, const float* taps, int ntaps, int up,
                       int down, float* y, long long n0, int ny, long long ldy, int B, void* stream);
 
+/* ---- crop + augment gather of a training batch (data.py: SequenceDataset.sample_batch; the
+ * reference augments on disk, augment_data.py) ------------------------------------------------------------------------
+ * poses (frames, C) fp32: the takes of the dataset back to back, C a multiple of 3 (joint j = columns 3j .. 3j + 2 =
+ * x, y, z; y is the vertical axis). track (samples) fp32: their audio tracks back to back, or NULL with S == 0 (the
+ * audio-less loaders). rows: DEVICE array of B records, filled by the host:
+ *   pose_start              row of the store that output frame 0 shows; pose_first / pose_last: the first and the last
+ *                           row of the row's own take (inclusive)
+ *   audio_start             sample of the store that output sample 0 sits on; audio_first / audio_last: the first and
+ *                           the last sample of the row's own take (inclusive)
+ *   a, b                    playback speed a / b, reduced, 1 <= a, b <= 64
+ *   tap_offset, ntaps       the row's filter taps[tap_offset .. tap_offset + ntaps) in the concatenated tap buffer
+ *                           (ntaps odd, <= 1281; not read at speed 1/1)
+ *   mirror, cos_yaw, sin_yaw, gain
+ * out_poses (B, T, C): frame i of row r shows source position pose_start + i a / b: j = (i a) div b, f = ((i a) mod b) /
+ *   b; v = x[j] when f == 0, else fmaf(f, x[j + 1] - x[j], x[j]) (j + 1 clamped to pose_last, read only when f != 0).
+ *   With mirror == 0, cos_yaw == 1 and sin_yaw == 0 the output is v. Otherwise per joint, with u = (v - shift[col]) /
+ *   scale[col]: ux = -ux under mirror; x' = fmaf(c, ux, s uz), z' = fmaf(c, uz, -(s ux)), y' = uy; out = fmaf(u',
+ *   scale[col], shift[col]). scale, shift: C floats each.
+ * out_audio (B, S): m2d_resample_poly's formula with up = b, down = a on X[m] = track[audio_start + m] where that
+ *   index lies in [audio_first, audio_last], zero elsewhere: t = n a + half, half = (ntaps - 1) / 2,
+ *   y[n] = gain * sum over m with 0 <= t - m b < ntaps of taps[t - m b] X[m] - one fp32 accumulator, fmaf in ascending
+ *   tap index, then one multiply by gain: with gain == 1 the bits of m2d_resample_poly on the take alone. Speed 1/1:
+ *   y[n] = gain X[n].
+ * All source indexing is 64-bit; every read lies inside the row's own take (and inside the store, whatever the table
+ * says). One launch on `stream`, no workspace, no atomics: an output element is a bit-level pure function of its row's
+ * record and its index, whatever B, the row's position and the launch's tiling. A record the Python wrapper would have
+ * refused (a or b outside [1, 64], bad taps) gives NaN, never a stray read.
+ * M2D_ERR_ARG (nothing launched): B, T or C <= 0; S < 0; C % 3 != 0; a null pose store, table, scale, shift or
+ * out_poses, or frames <= 0; S > 0 with a null track store, taps or out_audio, or samples or taps_total <= 0. */
+typedef struct M2dAugmentRow {
+  long long pose_start, pose_first, pose_last;
+  long long audio_start, audio_first, audio_last;
+  int a, b, tap_offset, ntaps, mirror;
+  float cos_yaw, sin_yaw, gain;
+} M2dAugmentRow;
+int m2d_crop_augment(const float* poses, long long frames, int C, const float* track, long long samples,
+                     const M2dAugmentRow* rows, const float* scale, const float* shift, const float* taps,
+                     int taps_total, float* out_poses, float* out_audio, int B, int T, int S, void* stream);
+
 /* ---- beat alignment of a dance with its music (metrics.py; no counterpart in the reference) --
  * STFT band energies. n_fft: a power of two in [256, 2048]; nbins = n_fft / 2 + 1; w[n] = 0.5 - 0.5 cos(2 pi n / n_fft)
  * (periodic Hann). Row b of x (B rows, ldx floats apart) holds samples [0, S) of a track, every other sample is zero.

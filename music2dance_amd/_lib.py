@@ -124,6 +124,7 @@ SIGNATURES = {
     "m2d_jpeg_encode": (_I, [_F, _L, _I, _I, _c.c_char_p, _F, _c.c_longlong, _F, _F, _S, _F]),
     "m2d_resample_poly": (_I, [_F, _c.c_longlong, _I, _c.c_longlong, _F, _I, _I, _I, _F, _c.c_longlong, _I, _c.c_longlong,
                                 _I, _F]),
+    "m2d_crop_augment": (_I, [_F, _c.c_longlong, _I, _F, _c.c_longlong, _F, _F, _F, _F, _I, _F, _F, _I, _I, _I, _F]),
     "m2d_stft_image_elems": (_S, [_I]),
     "m2d_stft_pack_basis": (_I, [_F, _I, _F, _F]),
     "m2d_stft_bands": (_I, [_F, _c.c_longlong, _I, _I, _c.c_longlong, _I, _I, _I, _F, _F, _I, _F, _F]),

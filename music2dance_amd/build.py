@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libm2d_hip.so")
 SOURCES = ["m2d_runtime.hip", "gemm_engine.hip", "conv1d.hip", "tcn.hip", "probe_gemm.hip", "conv1d_thin.hip", "bn.hip", "gru.hip",
-           "pointwise.hip", "cond.hip", "render.hip", "jpeg.hip", "resample.hip", "spectral.hip", "distrib.hip", "knn.hip"]
+           "pointwise.hip", "cond.hip", "render.hip", "jpeg.hip", "resample.hip", "augment.hip", "spectral.hip", "distrib.hip", "knn.hip"]
 # the sources that carry -DM2D_STAMP instrumentation (the stamped variant reuses every other object)
 STAMPED = ["gemm_engine.hip", "tcn.hip"]
 STAMP_LIB_PATH = os.path.join(LIB_DIR, "libm2d_hip_stamp.so")

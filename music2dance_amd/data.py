@@ -14,10 +14,15 @@ What differs from the reference, on purpose:
     one masked gather, on the device when asked (default: host tensors, as the reference returns them), and
     `SequenceDataset.sample_batch(indices, device=)` cuts a whole batch of windows out of the HBM-resident store;
   * `SequenceDataset(crop_rng=)`: an explicit generator for the window starts (default: numpy's global one, as in the
-    reference); `make_loaders` returns no validation loader when the hold-out is empty.
+    reference); `make_loaders` returns no validation loader when the hold-out is empty;
+  * `SequenceDataset(augment=)` / the YAML's `dataset: augment:` (off by default): training windows under a drawn
+    playback speed, mirror, yaw and audio gain - the rule is `augment_window` (host, fp64), the resident gather applies
+    it in one HIP launch (m2d_crop_augment). The reference augments on disk (augment_data.py: mirrored waltz copies).
 Nothing here is on the timed path; the kernels it calls are declared in include/m2d.h.
 """
+import collections
 import json
+import math
 import os
 import pickle
 
@@ -221,6 +226,163 @@ def retime_sequence(frames, new_len):
     return np.where(f < np.finfo(np.float64).eps, x[i], x[i] + f * (x[nxt] - x[i]))
 
 
+# --------------------------------------------------------------------------------------- augmentation
+# One rule, stated here on the host in fp64 (augment_window); kernels.crop_augment (m2d_crop_augment) applies it inside
+# the resident gather in fp32. DESIGN.md section 19.
+AugmentParams = collections.namedtuple("AugmentParams", "a b mirror cos sin gain")
+AugmentParams.__doc__ = """One row's augmentation: playback speed a / b (reduced, max(a, b) <= 64), mirror flag (x -> -x),
+(cos, sin) of the yaw about the vertical (y) axis, audio gain factor."""
+IDENTITY = AugmentParams(1, 1, False, 1.0, 0.0, 1.0)
+MAX_SPEED_TERM = 64
+
+
+def parse_speed(speed):
+    """'a/b' (or a pair) -> (a, b): positive integers, reduced by their gcd, max(a, b) <= 64"""
+    try:
+        a, b = (int(v) for v in (speed.split("/") if isinstance(speed, str) else speed))
+    except (TypeError, ValueError):
+        raise ValueError("augment: a speed is 'a/b' with integers a and b, got %r" % (speed,))
+    if a < 1 or b < 1 or max(a, b) > MAX_SPEED_TERM:
+        raise ValueError("augment: speed %r: a and b must lie in [1, %d]" % (speed, MAX_SPEED_TERM))
+    if math.gcd(a, b) != 1:
+        raise ValueError("augment: speed %r is not reduced by its gcd (write %d/%d)" % (speed, a // math.gcd(a, b),
+                                                                                     b // math.gcd(a, b)))
+    return a, b
+
+
+def frames_needed(T, a, b):
+    """source frames a window of T output frames at speed a / b reads: ceil((T - 1) a / b) + 1"""
+    return -(-(int(T) - 1) * int(a) // int(b)) + 1
+
+
+def speed_taps(a, b):
+    """The filter of the audio leg at speed a / b, fp64 values of the fp32 taps the device holds: audio.design_taps(b, a)
+    (up = b, down = a), the one-tap identity at 1/1"""
+    if a == b:
+        return np.ones(1)
+    from .audio import design_taps
+    return design_taps(b, a)[2].astype(np.float32).astype(np.float64)
+
+
+class Augment:
+    """The YAML's `dataset: augment:` block -> per-row draws. Keys (all optional): mirror (probability of x -> -x, in
+    [0, 1]), yaw_deg (yaw uniform in [-yaw_deg, +yaw_deg] about the vertical axis, >= 0), speeds (list of 'a/b' drawn
+    uniformly), gain_db (audio gain uniform in [-gain_db, +gain_db] dB, >= 0), seed. The mirror negates x and does NOT
+    exchange left and right joints: the dataset's joint names are in neither repository.
+    Draws come from an own numpy Generator(seed); every row takes the same four uniforms in the same order - speed index,
+    mirror, yaw, gain - whatever is switched off, so the stream does not shift with the configuration."""
+    KEYS = ("mirror", "yaw_deg", "speeds", "gain_db", "seed")
+
+    def __init__(self, cfg=None):
+        cfg = dict(cfg or {})
+        unknown = sorted(set(cfg) - set(self.KEYS))
+        if unknown:
+            raise ValueError("augment: unknown key(s) %s (known: %s)" % (", ".join(unknown), ", ".join(self.KEYS)))
+        self.mirror = float(cfg.get("mirror") or 0.0)
+        self.yaw_deg = float(cfg.get("yaw_deg") or 0.0)
+        self.gain_db = float(cfg.get("gain_db") or 0.0)
+        self.seed = int(cfg.get("seed") or 0)
+        if not 0.0 <= self.mirror <= 1.0:
+            raise ValueError("augment: mirror is a probability in [0, 1], got %r" % cfg.get("mirror"))
+        if not (self.yaw_deg >= 0.0 and math.isfinite(self.yaw_deg)):
+            raise ValueError("augment: yaw_deg must be >= 0, got %r" % cfg.get("yaw_deg"))
+        if not (self.gain_db >= 0.0 and math.isfinite(self.gain_db)):
+            raise ValueError("augment: gain_db must be >= 0, got %r" % cfg.get("gain_db"))
+        speeds = cfg.get("speeds")
+        if isinstance(speeds, str):
+            speeds = [speeds]
+        self.speeds = tuple(parse_speed(s) for s in (speeds or ["1/1"]))
+        self.rng = np.random.Generator(np.random.PCG64(self.seed))
+
+    def draw(self, n):
+        """-> n AugmentParams, row by row; cos and sin are taken here in fp64 (the device never calls sincos)"""
+        rows = []
+        for _ in range(int(n)):
+            u = [float(v) for v in self.rng.random(4)]
+            a, b = self.speeds[min(int(u[0] * len(self.speeds)), len(self.speeds) - 1)]
+            theta = math.radians((2.0 * u[2] - 1.0) * self.yaw_deg)
+            gain = 10.0 ** ((2.0 * u[3] - 1.0) * self.gain_db / 20.0)
+            rows.append(AugmentParams(a, b, bool(u[1] < self.mirror), math.cos(theta), math.sin(theta), gain))
+        return rows
+
+
+def _is_identity_pose(p):
+    return not p.mirror and p.cos == 1.0 and p.sin == 0.0
+
+
+def augment_window(poses_take, track_take, p0, T, S, hop, params, scaler):
+    """THE rule, host fp64: the window of T frames (and S samples) that starts at frame p0 (sample p0 hop) of one take,
+    under `params` -> (poses (T, J, 3), audio (S,) or None when track_take is None).
+    Poses: output frame i shows source position p0 + i a / b in exact integers, j = (i a) div b, f = ((i a) mod b) / b:
+    x[j] when f == 0, else x[j] + f (x[j + 1] - x[j]) (retime_sequence's recipe with an exact fraction), interpolated in
+    the stored (scaled) values; then, unless the transform is the identity: un-scale per column (v - min_) / scale_,
+    x -> -x under the mirror, x' = c x + s z, z' = -s x + c z (y, column 1 of a joint, is the vertical axis and the
+    skeletons are centred on the body), scale again; no clamp to [0, 1]. scaler None: scale 1, shift 0.
+    Audio: output n sits at source time p0 hop + n a / b: m2d_resample_poly's formula with up = b, down = a and
+    speed_taps(a, b), y[n] = gain sum_m taps[n a + half - m b] X[m], X[m] = sample p0 hop + m of the take, zero outside
+    the take (m may be negative); 1/1: gain X[n]."""
+    a, b = int(params.a), int(params.b)
+    x = np.asarray(poses_take, dtype=np.float64)
+    L = len(x)
+    x = x.reshape(L, -1)
+    p0, T, S, hop = int(p0), int(T), int(S), int(hop)
+    if p0 < 0 or p0 + frames_needed(T, a, b) > L:
+        raise ValueError("augment_window: %d frames from %d at speed %d/%d do not fit a take of %d frames"
+                         % (T, p0, a, b, L))
+    ia = np.arange(T, dtype=np.int64) * a
+    j, r = p0 + ia // b, ia % b
+    f = (r / float(b))[:, None]
+    nxt = np.minimum(j + 1, L - 1)
+    v = np.where(f == 0.0, x[j], x[j] + f * (x[nxt] - x[j]))
+    if not _is_identity_pose(params):
+        scale = 1.0 if scaler is None else np.asarray(scaler.scale_, dtype=np.float64)
+        shift = 0.0 if scaler is None else np.asarray(scaler.min_, dtype=np.float64)
+        u = ((v - shift) / scale).reshape(T, -1, 3)
+        ux = -u[..., 0] if params.mirror else u[..., 0]
+        uz = u[..., 2]
+        c, s = float(params.cos), float(params.sin)
+        u = np.stack((c * ux + s * uz, u[..., 1], -s * ux + c * uz), axis=-1)
+        v = u.reshape(T, -1) * scale + shift
+    poses = v.reshape(T, -1, 3)
+    if track_take is None:
+        return poses, None
+    X = np.asarray(track_take, dtype=np.float64)
+    a0, g = p0 * hop, float(params.gain)
+
+    def sample(idx):
+        inside = (idx >= 0) & (idx < len(X))
+        return np.where(inside, X[np.clip(idx, 0, max(len(X) - 1, 0))] if len(X) else 0.0, 0.0)
+
+    n = np.arange(S, dtype=np.int64)
+    if a == b:
+        return poses, g * sample(a0 + n)
+    taps = speed_taps(a, b)
+    t = n * a + (len(taps) - 1) // 2
+    q, phi = t // b, t % b
+    jj = np.arange(-(-len(taps) // b), dtype=np.int64)[None, :]
+    k = phi[:, None] + jj * b
+    h = np.where(k < len(taps), taps[np.minimum(k, len(taps) - 1)], 0.0)
+    return poses, g * (h * sample(a0 + q[:, None] - jj)).sum(axis=1)
+
+
+_TAP_BANKS = {}
+
+
+def _tap_bank(device, speeds):
+    """The taps of every speed but 1/1 end to end in one fp32 device buffer -> (buffer, {(a, b): (offset, ntaps)})"""
+    key = (str(device), tuple(sorted(set(s for s in speeds if s[0] != s[1]))))
+    bank = _TAP_BANKS.get(key)
+    if bank is None:
+        parts, where, off = [np.zeros(1)], {}, 1    # (never empty: the kernel's audio form wants a tap buffer)
+        for a, b in key[1]:
+            t = speed_taps(a, b)
+            where[(a, b)] = (off, len(t))
+            parts.append(t)
+            off += len(t)
+        bank = _TAP_BANKS[key] = (torch.as_tensor(np.concatenate(parts), dtype=torch.float32).to(device), where)
+    return bank
+
+
 # --------------------------------------------------------------------------------------- datasets
 # Storage is columnar: every take of a dataset lives in ONE array, takes back to back, with an offsets table - poses
 # (sum of frames, 23, 3) and audio (sum of samples,). `sequences` / `musics` hand out per-take views of those arrays
@@ -337,10 +499,15 @@ class SequenceDataset(Dataset):
     `crop_rng` (extension): a numpy RandomState / Generator the window starts are drawn from; default = numpy's global
     generator, which is what the reference draws from (utils.py:245-248), so seeded runs crop identically.
     `sync` (extension): trim the takes that have an accepted sync.json (load_all; the YAML key dataset.sync, off by
-    default)."""
+    default).
+    `augment` (extension): None (off: every path is what it is without the argument), an `Augment` or the dict it is made
+    from (the YAML key dataset.augment). An item is then a window under freshly drawn AugmentParams: `sample_batch` on a
+    HIP device draws on the host, uploads one small table and makes ONE m2d_crop_augment launch; on the host
+    (`device=None`, `__getitem__`) the same rule runs in fp64 (augment_window). A window at speed a / b needs
+    frames_needed(T, a, b) frames and its start is drawn, after the row's parameters, from [0, L - need)."""
 
     def __init__(self, name, config, resume=False, scaler=None, dance_types=("W", "C", "R", "T"), withaudio=False,
-                 crop_rng=None, sync=False):
+                 crop_rng=None, sync=False, augment=None):
         self.aud_rate, self.vid_rate = config["audio_rate"], config["video_rate"]
         self.seq_length, self.feat_size = config["seq_length"], config["feat_size"]
         self.stick_length = int(self.seq_length * self.vid_rate)
@@ -349,6 +516,8 @@ class SequenceDataset(Dataset):
         self.withaudio = withaudio
         self.crop_rng = crop_rng
         self.scaler = scaler
+        self.augment = Augment(augment) if isinstance(augment, dict) else augment
+        self.pose_scaler = scaler   # the scaler the stored poses are in (a subset keeps it; its `scaler` stays None)
         if resume:
             poses, self.labels, self.dirs = name["sequences"], name["labels"], name["dirs"]
             tracks = name["musics"] if withaudio else None
@@ -385,8 +554,88 @@ class SequenceDataset(Dataset):
         draw = getattr(rng, "integers", None) or rng.randint
         return int(draw(0, span))
 
+    # ---- augmented windows (self.augment set)
+    def _draw_start_for(self, idx, p):
+        """the start of a window at speed p.a / p.b, from [0, L - need) (at 1/1 the draw of _draw_start)"""
+        L = int(self._poses.starts[idx + 1] - self._poses.starts[idx])
+        need = frames_needed(self.stick_length, p.a, p.b)
+        if L <= need:
+            raise ValueError("take %s has %d frames: a window of %d frames at speed %d/%d needs more than %d"
+                             % (self.dirs[idx], L, self.stick_length, p.a, p.b, need))
+        rng = self.crop_rng if self.crop_rng is not None else np.random
+        draw = getattr(rng, "integers", None) or rng.randint
+        return int(draw(0, L - need))
+
+    def _unit_coeffs(self, device):
+        """scale 1 and shift 0 on `device`: the kernel's scaler when the poses are stored unscaled"""
+        c = getattr(self, "_unit", None)
+        if c is None or c[0].device != torch.device(device) or c[0].numel() != self._pose_columns():
+            n = self._pose_columns()
+            c = self._unit = (torch.ones(n, dtype=torch.float32, device=device),
+                              torch.zeros(n, dtype=torch.float32, device=device))
+        return c
+
+    def _pose_columns(self):
+        return int(np.prod(self._poses.flat.shape[1:]))
+
+    def gather_augmented(self, indices, firsts, params, device=None):
+        """The windows of takes `indices` that start at frames `firsts`, under `params` (one AugmentParams a row) ->
+        (poses (B, T, J, 3) fp32, audio (B, S) fp32 or None without audio). On a HIP `device`: the per-row table of
+        include/m2d.h and one m2d_crop_augment launch over the resident store; else augment_window row by row."""
+        T, S, hop = self.stick_length, self.audio_length if self.withaudio else 0, self.ratio
+        where = torch.device(device if device is not None else "cpu")
+        if where.type != "cuda":
+            rows = [augment_window(self._poses[i], self._tracks[i] if self.withaudio else None, f, T, S, hop, p,
+                                   self.pose_scaler) for i, f, p in zip(indices, firsts, params)]
+            poses = torch.as_tensor(np.stack([r[0] for r in rows]), dtype=torch.float32)
+            audio = torch.as_tensor(np.stack([r[1] for r in rows]), dtype=torch.float32) if self.withaudio else None
+            return poses, audio
+        table = np.zeros(len(indices), dtype=kernels.AUGMENT_ROW)
+        idx = np.asarray(indices, dtype=np.int64)
+        table["pose_first"] = self._poses.starts[idx]
+        table["pose_last"] = self._poses.starts[idx + 1] - 1
+        table["pose_start"] = table["pose_first"] + np.asarray(firsts, dtype=np.int64)
+        bank, slots = (None, {})
+        if self.withaudio:
+            table["audio_first"] = self._tracks.starts[idx]
+            table["audio_last"] = self._tracks.starts[idx + 1] - 1
+            table["audio_start"] = table["audio_first"] + np.asarray(firsts, dtype=np.int64) * hop
+            speeds = self.augment.speeds if self.augment is not None else ()
+            if any((p.a, p.b) not in speeds for p in params):
+                speeds = tuple(speeds) + tuple((p.a, p.b) for p in params)
+            bank, slots = _tap_bank(where, speeds)
+        for r, p in enumerate(params):
+            table[r]["a"], table[r]["b"], table[r]["mirror"] = p.a, p.b, bool(p.mirror)
+            table[r]["tap_offset"], table[r]["ntaps"] = slots.get((p.a, p.b), (0, 1))
+            table[r]["cos_yaw"], table[r]["sin_yaw"], table[r]["gain"] = p.cos, p.sin, p.gain
+        scale, shift = self.pose_scaler._coeffs(where, False) if self.pose_scaler is not None else self._unit_coeffs(where)
+        store = self._poses.device(where)
+        poses, audio = kernels.crop_augment(store.view(store.shape[0], -1),
+                                            self._tracks.device(where) if self.withaudio else None, table, scale,
+                                            shift, bank, T, S)
+        return poses.view(len(indices), T, *store.shape[1:]), audio
+
+    def _sample_batch_augmented(self, indices, device):
+        params = self.augment.draw(len(indices))
+        firsts = [self._draw_start_for(i, p) for i, p in zip(indices, params)]
+        poses, audio = self.gather_augmented(indices, firsts, params, device)
+        where = device if device is not None else "cpu"
+        labels = torch.as_tensor(np.asarray([self.labels[i] for i in indices]), device=where)
+        dirs = tuple(self.dirs[i] for i in indices)
+        lengths = [self.stick_length] * len(indices)
+        if not self.withaudio:
+            return poses, lengths, labels, dirs
+        return poses, lengths, audio, labels, dirs
+
     def __getitem__(self, idx):
         idx = int(idx)
+        if self.augment is not None:
+            p = self.augment.draw(1)[0]
+            first = self._draw_start_for(idx, p)
+            poses, audio = augment_window(self._poses[idx], self._tracks[idx] if self.withaudio else None, first,
+                                          self.stick_length, self.audio_length, self.ratio, p, self.pose_scaler)
+            item = [torch.from_numpy(poses)] + ([torch.from_numpy(audio).float()] if self.withaudio else [])
+            return (*item, torch.as_tensor(np.asarray(self.labels[idx])), self.dirs[idx])
         first = self._draw_start(idx)
         item = [torch.from_numpy(self._poses[idx][first:first + self.stick_length])]
         if self.withaudio:
@@ -399,6 +648,8 @@ class SequenceDataset(Dataset):
         the order of `indices`, and same result as collate_fn([self[i] for i in indices], device=device) (all windows
         have equal length, so the collate step's sort is the identity): (poses, lengths, [audio,] labels, dirs)."""
         indices = [int(i) for i in indices]
+        if self.augment is not None:
+            return self._sample_batch_augmented(indices, device)
         firsts = np.asarray([self._draw_start(i) for i in indices], dtype=np.int64)
         rows = self._poses.starts[indices] + firsts
         where = device if device is not None else "cpu"
@@ -428,8 +679,10 @@ class SequenceDataset(Dataset):
         self._tracks.keep_heads((seconds * self.aud_rate).astype(np.int64))
         self._poses.keep_heads((seconds * self.vid_rate).astype(np.int64))
 
-    def subset(self, indices, withaudio=None):
-        """A dataset over the takes `indices` (same rates / crop source)."""
+    def subset(self, indices, withaudio=None, augment=None):
+        """A dataset over the takes `indices` (same rates / crop source). `augment`: the subset's augmentation - the
+        default DROPS it (a validation or classifier subset is never augmented; make_loaders hands the dataset's own to
+        the train subset only)."""
         withaudio = self.withaudio if withaudio is None else withaudio
         state = {"sequences": [self._poses[i] for i in indices], "labels": [self.labels[i] for i in indices],
                  "dirs": [self.dirs[i] for i in indices]}
@@ -437,7 +690,9 @@ class SequenceDataset(Dataset):
             state["musics"] = [self._tracks[i] for i in indices]
         cfg = {"audio_rate": self.aud_rate, "video_rate": self.vid_rate, "seq_length": self.seq_length,
                "feat_size": self.feat_size}
-        return SequenceDataset(state, cfg, resume=True, withaudio=withaudio, crop_rng=self.crop_rng)
+        sub = SequenceDataset(state, cfg, resume=True, withaudio=withaudio, crop_rng=self.crop_rng, augment=augment)
+        sub.pose_scaler = self.pose_scaler
+        return sub
 
     def export(self, pathfile):
         with open(pathfile, "wb") as f:
@@ -536,17 +791,19 @@ def make_loaders(dataset, batch_size, withaudio=True, logdir=None, device=None):
         with open(os.path.join(logdir, "trainvaltest_samples.json"), "w") as f:
             json.dump({k + "_samples": [dataset.dirs[i] for i in v] for k, v in parts.items()}, f)
 
-    def loader(idx, per_batch):
+    def loader(idx, per_batch, augment=None):
         if not idx:
             return None
         weights = class_balanced_weights(dataset.labels, idx)
         sampler = WeightedRandomSampler(weights, len(weights))
         if device is not None:
-            return ResidentLoader(dataset.subset(idx, withaudio), per_batch, sampler, device)
-        return DataLoader(dataset.subset(idx, withaudio), batch_size=per_batch, sampler=sampler,
+            return ResidentLoader(dataset.subset(idx, withaudio, augment=augment), per_batch, sampler, device)
+        return DataLoader(dataset.subset(idx, withaudio, augment=augment), batch_size=per_batch, sampler=sampler,
                           collate_fn=lambda b: collate_fn(b, withaudio=withaudio))
 
-    return loader(parts["train"], batch_size), loader(parts["val"], len(parts["val"])), tuple(parts.values())
+    # (only the train subset is augmented)
+    return (loader(parts["train"], batch_size, getattr(dataset, "augment", None)),
+            loader(parts["val"], len(parts["val"])), tuple(parts.values()))
 
 
 # --------------------------------------------------------------------------------------- synthetic dataset folder

@@ -10,8 +10,10 @@ the entry point's name; the weight images the GEMMs read are kept by `HipKernels
 """
 import contextlib
 import ctypes
+import math
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib, levers
@@ -1536,3 +1538,69 @@ def set_impl(obj):
     prev = _impl
     _impl = obj
     return prev
+
+
+# ---------------------------------------------------------------- the loaders' crop + augment gather (data.py)
+# struct M2dAugmentRow of include/m2d.h, as the numpy record the host fills: one row of the batch
+AUGMENT_ROW = np.dtype([("pose_start", "<i8"), ("pose_first", "<i8"), ("pose_last", "<i8"), ("audio_start", "<i8"),
+                        ("audio_first", "<i8"), ("audio_last", "<i8"), ("a", "<i4"), ("b", "<i4"),
+                        ("tap_offset", "<i4"), ("ntaps", "<i4"), ("mirror", "<i4"), ("cos_yaw", "<f4"),
+                        ("sin_yaw", "<f4"), ("gain", "<f4")])
+assert AUGMENT_ROW.itemsize == 80
+AUGMENT_MAX_RATIO, AUGMENT_MAX_TAPS = 64, 1281
+
+
+def crop_augment(poses, track, table, scale, shift, taps, T, S):
+    """m2d_crop_augment: poses (frames, C) fp32 store, track (samples,) fp32 store or None (then S == 0), table: HOST
+    numpy array of B AUGMENT_ROW records, scale / shift (C,), taps: the concatenated tap buffer (1-D; None without audio)
+    -> (out_poses (B, T, C), out_audio (B, S) or None). The table's contents are checked HERE, before anything is
+    uploaded or launched (the library sees only a device pointer): a reduced speed with terms in [1, 64], a window that
+    lies inside its own take and a take that lies inside the store, odd tap counts inside the tap buffer, finite factors.
+    A module function, not a HipKernels method: the loaders' host path never comes here (it runs data.augment_window), so
+    the CPU stand-ins of the kernel layer have no counterpart of it."""
+    name = "crop_augment"
+    dev = _chk(poses, track, scale, shift, taps)
+    T, S = int(T), int(S)
+    if poses.dim() != 2 or poses.shape[0] < 1:
+        raise _lib.M2dError("%s: the pose store must be a non-empty (frames, C) tensor" % name)
+    frames, C = poses.shape
+    if scale.numel() != C or shift.numel() != C:
+        raise _lib.M2dError("%s: scale and shift must hold C = %d values" % (name, C))
+    if not isinstance(table, np.ndarray) or table.dtype != AUGMENT_ROW or table.ndim != 1:
+        raise _lib.M2dError("%s: the table must be a 1-D numpy array of kernels.AUGMENT_ROW records" % name)
+    if S > 0 and (track is None or taps is None or track.dim() != 1 or taps.dim() != 1 or track.numel() < 1):
+        raise _lib.M2dError("%s: S > 0 needs a 1-D track store and a 1-D tap buffer" % name)
+    if S == 0:
+        track = taps = None
+    B = len(table)
+    if B > 0 and T > 0:   # (B, T <= 0: the library refuses)
+        a, b = table["a"].astype(np.int64), table["b"].astype(np.int64)
+        if ((a < 1) | (b < 1) | (a > AUGMENT_MAX_RATIO) | (b > AUGMENT_MAX_RATIO)).any():
+            raise _lib.M2dError("%s: a speed a / b needs 1 <= a, b <= %d" % (name, AUGMENT_MAX_RATIO))
+        if any(math.gcd(int(x), int(y)) != 1 for x, y in zip(a, b)):
+            raise _lib.M2dError("%s: a speed a / b must be reduced by its gcd" % name)
+        need = -(-(T - 1) * a // b) + 1
+        first, last, start = table["pose_first"], table["pose_last"], table["pose_start"]
+        if ((first < 0) | (last >= frames) | (start < first) | (start + need - 1 > last)).any():
+            raise _lib.M2dError("%s: a pose window leaves its take, or a take leaves the store of %d frames"
+                                % (name, frames))
+        if not (np.isfinite(table["cos_yaw"]) & np.isfinite(table["sin_yaw"]) & np.isfinite(table["gain"])).all():
+            raise _lib.M2dError("%s: cos, sin and gain must be finite" % name)
+        if S > 0:
+            first, last, start = table["audio_first"], table["audio_last"], table["audio_start"]
+            if ((first < 0) | (last >= track.numel()) | (start < first) | (start > last)).any():
+                raise _lib.M2dError("%s: an audio window starts outside its take, or a take leaves the store of %d "
+                                    "samples" % (name, track.numel()))
+            off, nt = table["tap_offset"].astype(np.int64), table["ntaps"].astype(np.int64)
+            resampled = a != b
+            if (resampled & ((nt < 1) | (nt % 2 == 0) | (nt > AUGMENT_MAX_TAPS) | (off < 0)
+                             | (off + nt > taps.numel()))).any():
+                raise _lib.M2dError("%s: a row's taps must be an odd number <= %d inside the tap buffer of %d"
+                                    % (name, AUGMENT_MAX_TAPS, taps.numel()))
+    rows = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8)).to(dev) if B > 0 else None
+    out = torch.empty((max(B, 0), max(T, 0), C), dtype=torch.float32, device=dev)
+    audio = torch.empty((B, S), dtype=torch.float32, device=dev) if S > 0 else None
+    _launch("m2d_crop_augment", dev, _ptr(poses), frames, C, _ptr(track), 0 if track is None else track.numel(),
+            _ptr(rows), _ptr(scale), _ptr(shift), _ptr(taps), 0 if taps is None else taps.numel(), _ptr(out),
+            _ptr(audio), B, T, S)
+    return out, audio

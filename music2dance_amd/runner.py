@@ -243,13 +243,15 @@ def subset_loader(run, dataset, batch_size, collate_fn=None):
 
 
 def sequence_dataset(run, withaudio):
-    """MinMax-scaled pose sequences (the scaler fitted on all still poses), random crops."""
+    """MinMax-scaled pose sequences (the scaler fitted on all still poses), random crops - augmented when the YAML has
+    a `dataset: augment:` block (data.Augment; phase 3's make_loaders keeps it to the train subset)."""
     from . import data as D
     folder = dataset_folder(run.cfg, run.opts.folder)
     print("Loading sticks and sequences datasets...")
     sticks = D.StickDataset(folder, normalize="minmax")
     return D.SequenceDataset(folder, run.cfg["dataset"], dance_types=run.cfg["dance_types"], scaler=sticks.scaler,
-                             withaudio=withaudio, sync=run.cfg["dataset"].get("sync", False))
+                             withaudio=withaudio, sync=run.cfg["dataset"].get("sync", False),
+                             augment=run.cfg["dataset"].get("augment"))
 
 
 def pose_sequence_loader(run, batch_size):
