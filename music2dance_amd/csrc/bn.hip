@@ -297,6 +297,7 @@ static int launch_reduce(BnReduceArgs& a, hipStream_t stream) {
     static const bool on = m2d_env_on("M2D_BN_VEC_ROWS");   // A/B lever
     const uintptr_t al = (uintptr_t)a.x | (uintptr_t)(a.mode == 1 ? a.dy : a.x) | (uintptr_t)((a.mode == 2 && a.mask) ? a.mask : a.x);
     a.vec_rows = (on && a.cpb > 1 && (a.L & 3) == 0 && (al & 15u) == 0) ? 1 : 0;
+    m2d_route_hit(a.vec_rows ? M2D_RT_bn_reduce_vec : M2D_RT_bn_reduce_scalar);
   }
   nsplit = m2d_ceil_div(a.B, a.rows_per_block);
   if (!a.ticket && hipMemsetAsync(a.acc, 0, sizeof(double) * 2 * a.C, stream) != hipSuccess)
@@ -738,8 +739,10 @@ static int bn_fwd_sums_begin(const char* who, const char* complaint, bool apply_
     a.fin_sums = sums; a.fin_count = count;
     a.fin_eps = eps; a.fin_momentum = momentum;
     a.fin_running_mean = running_mean; a.fin_running_var = running_var;
+    m2d_route_hit(M2D_RT_bn_fin_in_apply);
     return M2D_OK;
   }
+  m2d_route_hit(M2D_RT_bn_fin_launch);
   hipLaunchKernelGGL(m2d_bn_finalize_fwd_kernel, dim3(m2d_ceil_div(C, 256)), dim3(256), 0, stream, sums, save_mean,
                      save_invstd, running_mean, running_var, C, count, eps, momentum);
   M2D_CHECK_LAUNCH("m2d_bn_finalize_fwd_kernel");

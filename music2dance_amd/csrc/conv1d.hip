@@ -198,8 +198,10 @@ static int conv1d_fwd_impl(const float* x, const float* w, const float* w_packed
   if (Lout <= 0) M2D_FAIL(M2D_ERR_ARG, "m2d_conv1d_fwd: empty output (L=%d k=%d s=%d p=%d)", L, ks, stride, pad);
   if (!fits_i32((long long)B * Cin * L) || !fits_i32((long long)B * Cout * Lout))
     M2D_FAIL(M2D_ERR_RANGE, "m2d_conv1d_fwd: tensor exceeds 2^31 elements");
-  if (!residual && !sum_out && !out_mask && m2d_thin_long_applicable(Cin, Cout, ks, stride, pad, L))
+  if (!residual && !sum_out && !out_mask && m2d_thin_long_applicable(Cin, Cout, ks, stride, pad, L)) {
+    m2d_route_hit(M2D_RT_conv_to_thin_long);
     return m2d_thin_long_fwd(x, w, bias, y, B, L, ks, stride, pad, Lout, act, slope, wv, stats, ws, ws_bytes, (hipStream_t)stream);
+  }
   if (!residual && !sum_out && m2d_thin_applicable(Cin, Cout, ks, stride))
     return m2d_thin_fwd(x, w, bias, y, B, L, Cout, ks, stride, pad, Lout, act, slope, out_mask, out_mask_slope,
                         wv, stats, ws, ws_bytes, (hipStream_t)stream);
@@ -269,6 +271,7 @@ static int conv1d_fwd_impl(const float* x, const float* w, const float* w_packed
       t.B = B;
       t.Cin = Cin;
       t.L = L;
+      m2d_route_hit(M2D_RT_conv_to_tcn_fwd);
       return m2d_tcn_conv_launch(t, ks, nt, (hipStream_t)stream, "m2d_conv1d_fwd");
     }
   }
@@ -526,6 +529,7 @@ static int conv1d_bwd_data_impl(const float* dy, const float* w, const float* w_
     // dx[n, ci, s q + r - pad] = sum_{t, co} w[co, ci, r + s t] dy[n, co, q - t]: rows (ci, r), K = (t, co), columns (n, q)
     const int s = stride, nt = (ks + s - 1) / s;
     const bool tall = subpixel_tall(Cin, Cout, ks, s) && !dy_mask;  // (a masked dy runs on the register-staging kernel)
+    m2d_route_hit(tall ? M2D_RT_bwd_subpixel_tall : M2D_RT_bwd_subpixel_cir);
     const size_t pb = subpixel_bytes(Cout, Cin, ks, s);
     if (!ws || ws_bytes < pb) M2D_FAIL(M2D_ERR_WORKSPACE, "m2d_conv1d_bwd_data: workspace too small for the sub-pixel weights");
     {
@@ -637,11 +641,13 @@ static int conv1d_bwd_data_impl(const float* dy, const float* w, const float* w_
       t.B = B;
       t.Cin = Cout;
       t.L = L;
+      m2d_route_hit(M2D_RT_conv_to_tcn_bwd_data);
       return m2d_tcn_conv_launch(t, ks, nt, (hipStream_t)stream, "m2d_conv1d_bwd_data");
     }
   }
   // dx[n, ci, s*q + r - pad] = sum_{t, co} wb[ci, r + s*t, co] * dy[n, co, q - t] per output phase r:
   // K = (t, co), hi = t (taps(r) of them, resolved on the device), lo = co.
+  m2d_route_hit(M2D_RT_bwd_polyphase);
   p.bwd_data = 1;
   p.plan_kind = stride > 1 ? M2D_PLAN_BWD_DATA : M2D_PLAN_GENERAL;
   p.phases = stride;
@@ -793,6 +799,7 @@ static int conv1d_bwd_weight_impl(const float* x, const float* dy, float* dw, fl
     t.B = B;
     t.Cin = Cin;
     t.L = L;
+    m2d_route_hit(M2D_RT_conv_to_tcn_wgrad);
     return m2d_tcn_wgrad_launch(t, ks, ws, ws_bytes, (hipStream_t)stream, "m2d_conv1d_bwd_weight");
   }
   M2dGemmParams p;

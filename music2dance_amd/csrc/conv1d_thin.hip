@@ -634,8 +634,15 @@ static size_t thin_fwd_stats_part(int B, int Lout) { (void)B; (void)Lout; return
 size_t m2d_thin_fwd_stats_ws(int B, int Lout) { return thin_fwd_stats_part(B, Lout) + (size_t)256 * 32 * 2 * sizeof(double); }
 // workgroups of the persistent forward: one full-occupancy round (8 per CU: 18 KB of LDS, 35-50 registers), fewer when
 // there are not that many groups of four tiles. M2D_THIN_WG_PER_CU: A/B lever
-static int thin_fwd_grid(int total_tiles) {
+static int thin_wg_per_cu() {
   static const int per_cu = [] { const int v = m2d_env_int("M2D_THIN_WG_PER_CU", THIN_WPE); return v >= 1 && v <= 16 ? v : THIN_WPE; }();
+  return per_cu;
+}
+static std::atomic<int> g_thin_wg_per_cu{0};   // what the last LAUNCH's grid was sized with (0: none yet)
+// test-only, like m2d_debug_routes (not part of include/m2d.h)
+extern "C" int m2d_debug_thin_wg_per_cu(void) { return g_thin_wg_per_cu.load(std::memory_order_relaxed); }
+static int thin_fwd_grid(int total_tiles) {
+  const int per_cu = thin_wg_per_cu();
   const int need = m2d_ceil_div(total_tiles, 4), full = 256 * per_cu;
   return need < full ? need : full;
 }
@@ -660,6 +667,8 @@ int m2d_thin_fwd(const float* x, const float* w, const float* bias, float* y, in
   M2dProfScope prof(M2D_FAM_POINTWISE, stream, 2.0 * B * Lout * (double)Cout * ks,
                     4.0 * B * ((double)L + (double)Cout * Lout * (out_mask ? 2 : 1)), "thin_conv_fwd", Cout, B * Lout, ks);
   const int grid = thin_fwd_grid(total);
+  m2d_route_hit(M2D_RT_thin_persistent);
+  g_thin_wg_per_cu.store(thin_wg_per_cu(), std::memory_order_relaxed);
   hipLaunchKernelGGL((thin_fwd_mfma_kernel<25, 4>), dim3(grid), dim3(256), 0, stream, a, tpr, total);
   M2D_CHECK_LAUNCH("thin_fwd_mfma_kernel");
   if (stats)
@@ -855,6 +864,7 @@ static int thin_long_launch(const ThinArgs& a, int tpr, int total, hipStream_t s
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
   if (!attr_ok) M2D_FAIL(M2D_ERR_HIP, "m2d_conv1d_fwd (long single-channel kernel): cannot reserve %zu bytes of LDS", lds);
   const int grid = thin_long_grid(lds, total);
+  m2d_route_hit(M2D_RT_thin_long);
   *waves = grid * 8;
   hipLaunchKernelGGL((thin_long_fwd_kernel<KS, S>), dim3(grid), dim3(512), lds, stream, a, tpr, total);
   M2D_CHECK_LAUNCH("thin_long_fwd_kernel");

@@ -1934,6 +1934,9 @@ M2dGemmPlan m2d_gemm_plan(int M, int N, int nchunks, int phases, bool allow_spli
 template <int BM, bool AKF, bool BKF>
 static void launch_tile(const M2dGemmParams& p, dim3 grid, hipStream_t stream) {
   const bool masked = p.A.mask || p.B.mask;
+  static_assert(M2D_RT_gemm_reg_rr_masked == M2D_RT_gemm_reg_rr + 1 && M2D_RT_gemm_reg_kr_masked == M2D_RT_gemm_reg_kr + 1 &&
+                M2D_RT_gemm_reg_kk_masked == M2D_RT_gemm_reg_kk + 1, "a masked route follows its unmasked one");
+  m2d_route_hit((AKF ? (BKF ? M2D_RT_gemm_reg_kk : M2D_RT_gemm_reg_kr) : M2D_RT_gemm_reg_rr) + (masked ? 1 : 0));
   if (masked && p.O.wide) hipLaunchKernelGGL((m2d_gemm_kernel<BM, 128, AKF, BKF, true, true>), grid, dim3(256), 0, stream, p);
   else if (masked) hipLaunchKernelGGL((m2d_gemm_kernel<BM, 128, AKF, BKF, true, false>), grid, dim3(256), 0, stream, p);
   else if (p.O.wide) hipLaunchKernelGGL((m2d_gemm_kernel<BM, 128, AKF, BKF, false, true>), grid, dim3(256), 0, stream, p);
@@ -1968,17 +1971,20 @@ static int launch_maps(const M2dGemmParams& p, bool akf, bool bkf, dim3 grid, hi
     if (dl_enabled() && dl_eligible(p, akf, bkf)) {
       if constexpr (BM == 128) {
         if (p.tall_last_rb) {
+          m2d_route_hit(M2D_RT_gemm_dl_tall);
           hipLaunchKernelGGL(m2d_gemm_dl_tall_kernel, grid, dim3(256), 0, stream, p);
           return 0;
         }
         // eight waves per workgroup on the same tile (M2dTiling); the one-element epilogue does not fit the 64 VGPRs of
         // eight waves per SIMD without scratch: those launches (strided backward-data) keep four waves
         if (dl8_enabled() && (p.O.wide || (p.O.quad && p.splits <= 1))) {
+          m2d_route_hit(M2D_RT_gemm_dl8);
           if (p.O.wide) hipLaunchKernelGGL((m2d_gemm_dl_kernel<128, 128, 1, 8>), grid, dim3(512), 0, stream, p);
           else hipLaunchKernelGGL((m2d_gemm_dl_kernel<128, 128, 2, 8>), grid, dim3(512), 0, stream, p);
           return 0;
         }
       }
+      m2d_route_hit(BM == 128 ? M2D_RT_gemm_dl4_128 : M2D_RT_gemm_dl_small);
       if (p.O.wide) hipLaunchKernelGGL((m2d_gemm_dl_kernel<BM, 128, 1>), grid, dim3(256), 0, stream, p);
       else if (p.O.quad && p.splits <= 1) hipLaunchKernelGGL((m2d_gemm_dl_kernel<BM, 128, 2>), grid, dim3(256), 0, stream, p);
       else hipLaunchKernelGGL((m2d_gemm_dl_kernel<BM, 128, 0>), grid, dim3(256), 0, stream, p);
@@ -2204,6 +2210,12 @@ static int plan_and_launch(M2dGemmParams& p, PlanQuery& q, hipStream_t stream, d
   decide_wide(p, splits, ws);
   const dim3 grid((unsigned)m2d_ceil_div(p.N, 128), (unsigned)m2d_ceil_div(p.M, bm), (unsigned)(p.bwd_data ? p.phases : splits));
   M2dProfScope prof(M2D_FAM_GEMM, stream, flops, 0.0, what, p.M, p.N, p.K);
+  m2d_route_hit(p.O.wide ? M2D_RT_epi_wide : M2D_RT_epi_one);
+  if (splits > 1) m2d_route_hit(p.tickets ? M2D_RT_splitk_one_launch : M2D_RT_splitk_two_launch);
+  if (!p.tile_map) m2d_route_hit(M2D_RT_tile_map_off);
+  if (p.O.row_part && !p.stats_narrow_fast) m2d_route_hit(M2D_RT_stats_general);
+  if (p.O.row_part && splits > 1) m2d_route_hit(M2D_RT_stats_split);
+  if (q.k4) m2d_route_hit(p.k4_pair ? M2D_RT_k4_paired : M2D_RT_k4_plain);
   if (launch_grid(bm, grid)) M2D_FAIL(M2D_ERR_ARG, "%s: unsupported operand map combination", what);
   if (splits > 1 && !p.tickets) {
     const size_t total = (size_t)p.M * p.N;

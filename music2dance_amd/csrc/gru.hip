@@ -1084,11 +1084,13 @@ static int gru_stack_fwd(const char* name, const float* gi0, const float* const*
       GruPersistArgs pa;
       pa.s = a;
       gru_persist_fill(pa, ps);
+      m2d_route_hit(M2D_RT_gru_fwd_persistent);
       hipLaunchKernelGGL(persist_kernel, grid, dim3(64 * GRU_FWD_NW), GRU_PERSIST_FWD_LDS, stream, pa);
       M2D_CHECK_LAUNCH("m2d_gru_persist_fwd_kernel");
       return M2D_OK;
     }
   }
+  m2d_route_hit(M2D_RT_gru_fwd_steps);
   for (int d = 0; d < T + L - 1; ++d) {
     a.d = d;
     hipLaunchKernelGGL(step_kernel, grid, dim3(64 * GRU_FWD_NW), 0, stream, a);
@@ -1204,11 +1206,13 @@ int m2d_gru_stack_bwd(const float* dout, const float* const* out, const float* c
       pa.s = a;
       pa.counters = counters;
       gru_persist_fill(pa, ps);
+      m2d_route_hit(M2D_RT_gru_bwd_persistent);
       hipLaunchKernelGGL(m2d_gru_persist_bwd_kernel, grid, dim3(64 * GRU_BWD_NW), GRU_PERSIST_BWD_LDS, stream, pa);
       M2D_CHECK_LAUNCH("m2d_gru_persist_bwd_kernel");
       return M2D_OK;
     }
   }
+  m2d_route_hit(M2D_RT_gru_bwd_steps);
   for (int e = 0; e < T + L - 1; ++e) {
     a.e = e;
     hipLaunchKernelGGL(m2d_gru_stack_bwd_kernel, grid, dim3(64 * GRU_BWD_NW), 0, stream, a);
@@ -1492,6 +1496,7 @@ int m2d_gru_small_fwd(const float* gi, const float* w_hh, const float* b_hh, con
   if (B <= 0 || T <= 0 || !gru_small_fits(T, H)) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_fwd: bad shape");
   if (!gi || !w_hh || !b_hh || !h_n) M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_fwd: gi, w_hh, b_hh and h_n are required");
   M2dProfScope prof(M2D_FAM_GRU, stream, 2.0 * B * 3.0 * H * H * (double)T, 0.0, "gru_small_fwd", B, T, H);
+  m2d_route_hit(M2D_RT_gru_small);
   hipLaunchKernelGGL(m2d_gru_small_fwd_kernel, dim3(m2d_ceil_div(B, 4)), dim3(64), 0, stream, gi, w_hh, b_hh,
                      lengths, out, h_n, saved, B, T, H);
   M2D_CHECK_LAUNCH("m2d_gru_small_fwd_kernel");
@@ -1506,6 +1511,7 @@ int m2d_gru_small_bwd(const float* dout, const float* dh_n, const float* out, co
   if (!out || !saved || !w_hh || !dgi || !dgh)
     M2D_FAIL(M2D_ERR_ARG, "m2d_gru_small_bwd: out, saved, w_hh, dgi and dgh are required");
   M2dProfScope prof(M2D_FAM_GRU, stream, 2.0 * B * 3.0 * H * H * (double)T, 0.0, "gru_small_bwd", B, T, H);
+  m2d_route_hit(M2D_RT_gru_small);
   hipLaunchKernelGGL(m2d_gru_small_bwd_kernel, dim3(m2d_ceil_div(B, 4)), dim3(64), 0, stream, dout, dh_n, out,
                      saved, w_hh, lengths, dgi, dgh, B, T, H);
   M2D_CHECK_LAUNCH("m2d_gru_small_bwd_kernel");

@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 
 // the public C-ABI (error codes, struct M2dAdamItem, every entry point): each extern "C" definition is compiled against
 // its declaration, so one that disagrees with the header is a "conflicting types" error
@@ -82,6 +83,42 @@ static inline double m2d_env_double(const char* name, double dflt) {
   const char* e = m2d_env_raw(name);
   return e ? atof(e) : dflt;
 }
+
+// ---- route witness (host code; tests only) --------------------------------------------------------------------------
+// One process-wide counter per kernel form a launcher can choose, bumped on the host where the choice is made: the
+// suite asks them which kernel a call ran (tests/lever_cases.py, tests/test_gpu_levers.py). A relaxed increment per
+// launch, no lock, nothing on the device. m2d_debug_routes / m2d_debug_route_names (m2d_runtime.hip) read them; the
+// names are this list, in this order.
+#define M2D_ROUTES(X)                                                                                                  \
+  /* gemm_engine.hip, launch_maps: the kernel a tile launch runs */                                                    \
+  X(gemm_dl_tall) X(gemm_dl8) X(gemm_dl4_128) X(gemm_dl_small)                                                         \
+  X(gemm_reg_rr) X(gemm_reg_rr_masked) X(gemm_reg_kr) X(gemm_reg_kr_masked) X(gemm_reg_kk) X(gemm_reg_kk_masked)       \
+  /* plan_and_launch (both launchers): epilogue, split-K form, tile order, statistics */                               \
+  X(epi_wide) X(epi_one) X(splitk_one_launch) X(splitk_two_launch) X(tile_map_off)                            \
+  X(stats_general) X(stats_split) X(k4_paired) X(k4_plain)                                                             \
+  /* conv1d.hip: backward-data forms and the handovers to the dedicated kernels */                                     \
+  X(bwd_subpixel_tall) X(bwd_subpixel_cir) X(bwd_polyphase)                                                            \
+  X(conv_to_tcn_fwd) X(conv_to_tcn_bwd_data) X(conv_to_tcn_wgrad) X(conv_to_thin_long)                                 \
+  /* tcn.hip */                                                                                                        \
+  X(tcn_ns4) X(tcn_ns8) X(tcn_nt96) X(tcn_nt64) X(tcn_nt48) X(tcn_nt32) X(tcn_nt16) X(tcn_wgrad)                       \
+  /* conv1d_thin.hip */                                                                                                \
+  X(thin_long) X(thin_persistent)                                                                                      \
+  /* bn.hip */                                                                                                         \
+  X(bn_reduce_vec) X(bn_reduce_scalar) X(bn_fin_in_apply) X(bn_fin_launch)                                             \
+  /* pointwise.hip */                                                                                                  \
+  X(up_fwd_flat) X(up_fwd_vec) X(up_fwd_row) X(up_fwd_plain) X(up_bwd_flat) X(up_bwd_plain)                            \
+  /* gru.hip */                                                                                                        \
+  X(gru_fwd_persistent) X(gru_fwd_steps) X(gru_bwd_persistent) X(gru_bwd_steps) X(gru_small)
+
+enum M2dRoute {
+#define M2D_ROUTE_ENUM(name) M2D_RT_##name,
+  M2D_ROUTES(M2D_ROUTE_ENUM)
+#undef M2D_ROUTE_ENUM
+  M2D_RT_COUNT
+};
+
+extern std::atomic<unsigned long long> g_m2d_routes[M2D_RT_COUNT];   // m2d_runtime.hip
+static inline void m2d_route_hit(int route) { g_m2d_routes[route].fetch_add(1, std::memory_order_relaxed); }
 
 static inline int m2d_ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long m2d_ceil_div64(long long a, long long b) { return (a + b - 1) / b; }

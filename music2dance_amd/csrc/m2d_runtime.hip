@@ -9,6 +9,9 @@
 
 static thread_local char g_err[512] = "";
 
+// the route witness (m2d_common.h): zero-initialised, never reset
+std::atomic<unsigned long long> g_m2d_routes[M2D_RT_COUNT];
+
 void m2d_set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -113,6 +116,21 @@ int m2d_prof_end(double* out, int n_out) {
   for (auto& r : g_prof_recs) g_prof_pool.push_back({r.a, r.b});
   g_prof_recs.clear();
   return M2D_OK;
+}
+
+// test-only, like m2d_debug_force_plan (not part of include/m2d.h; tests/lever_cases.py binds them with ctypes); neither
+// touches a device. m2d_debug_routes copies the first min(n, M2D_RT_COUNT) counters and returns M2D_RT_COUNT;
+// m2d_debug_route_names gives their names, comma-separated, in the same order.
+int m2d_debug_routes(unsigned long long* out, int n) {
+  for (int i = 0; out && i < n && i < M2D_RT_COUNT; ++i) out[i] = g_m2d_routes[i].load(std::memory_order_relaxed);
+  return M2D_RT_COUNT;
+}
+
+const char* m2d_debug_route_names(void) {
+#define M2D_ROUTE_NAME(name) "," #name
+  static const char names[] = M2D_ROUTES(M2D_ROUTE_NAME);
+#undef M2D_ROUTE_NAME
+  return names + 1;
 }
 
 }  // extern "C"

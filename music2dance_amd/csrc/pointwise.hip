@@ -1021,17 +1021,21 @@ int m2d_upsample2_fwd_to(const float* x, float* y, size_t B, int C, int L, long 
     // (16-byte stores at flat offset 2 g, g even: aligned when every sample's block starts 16-byte aligned - dense blocks of
     // 2 C L floats with C L even, or a pitch that is a multiple of 4)
     const size_t pairs = B * (per_sample / 2);
+    m2d_route_hit(M2D_RT_up_fwd_flat);
     hipLaunchKernelGGL(m2d_upsample2_fwd_flat_kernel, dim3(grid_for(pairs, 16384)), dim3(256), 0, stream, x, y,
                        (unsigned)(per_sample / 2), pairs, L, yp);
   } else if ((L & 3) == 0 && L <= 1024 && (((uintptr_t)x | (uintptr_t)y) & 15u) == 0 && (yp & 3) == 0) {
     const size_t rpb = 256 / (L >> 2);
+    m2d_route_hit(M2D_RT_up_fwd_vec);
     hipLaunchKernelGGL(m2d_upsample2_fwd_vec_kernel, dim3(grid_for((rows + rpb - 1) / rpb * 256, 4096)), dim3(256), 0, stream,
                        x, y, rows, L, Cp, yp);
   } else if (L <= 256 && ((uintptr_t)y & 7u) == 0 && (yp & 1) == 0) {
     const size_t rpb = 256 / L;
+    m2d_route_hit(M2D_RT_up_fwd_row);
     hipLaunchKernelGGL(m2d_upsample2_fwd_row_kernel, dim3(grid_for((rows + rpb - 1) / rpb * 256, 8192)), dim3(256), 0, stream,
                        x, y, rows, L, Cp, yp);
   } else {
+    m2d_route_hit(M2D_RT_up_fwd_plain);
     hipLaunchKernelGGL(m2d_upsample2_fwd_kernel, dim3(grid_for(rows * 2 * L, 4096)), dim3(256), 0, stream, x, y, rows, L, Cp, yp);
   }
   M2D_CHECK_LAUNCH("m2d_upsample2_fwd");
@@ -1046,7 +1050,9 @@ int m2d_upsample2_bwd(const float* dy, float* dx, size_t rows, int L, void* stre
   if (rows == 0 || L <= 0) M2D_FAIL(M2D_ERR_ARG, "m2d_upsample2_bwd: bad shape");
   M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, 12.0 * rows * (double)L, "upsample2_bwd");
   const bool flat_on = upsample_flat_on();
-  if (flat_on && ((rows * (size_t)L) & 3) == 0 && (((uintptr_t)dy | (uintptr_t)dx) & 15u) == 0)
+  const bool flat = flat_on && ((rows * (size_t)L) & 3) == 0 && (((uintptr_t)dy | (uintptr_t)dx) & 15u) == 0;
+  m2d_route_hit(flat ? M2D_RT_up_bwd_flat : M2D_RT_up_bwd_plain);
+  if (flat)
     hipLaunchKernelGGL(m2d_upsample2_bwd_flat_kernel, dim3(grid_for(rows * L / 4, 16384)), dim3(256), 0, stream, dy, dx,
                        rows * L / 4, L);
   else

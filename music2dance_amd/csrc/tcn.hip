@@ -428,6 +428,8 @@ static int tcn_conv_launch_ns(const M2dTcnConv& p, hipStream_t stream, const cha
   const size_t lds = Cfg::lds_bytes(p.Cin);
   if (lds > 160 * 1024) M2D_FAIL(M2D_ERR_ARG, "%s: tile does not fit the LDS (%zu bytes)", what, lds);
   const unsigned tiles = (unsigned)(((long long)p.B * p.L + NT - 1) / NT);
+  m2d_route_hit(NS == 4 ? M2D_RT_tcn_ns4 : M2D_RT_tcn_ns8);
+  m2d_route_hit(NT == 96 ? M2D_RT_tcn_nt96 : NT == 64 ? M2D_RT_tcn_nt64 : NT == 48 ? M2D_RT_tcn_nt48 : NT == 32 ? M2D_RT_tcn_nt32 : M2D_RT_tcn_nt16);
   auto go = [&](auto kern) -> int {
     static bool attr_set = false;   // (per instantiation: the lambda's static is per closure type)
     if (!attr_set) {
@@ -829,6 +831,7 @@ int m2d_tcn_wgrad_launch(const M2dTcnWgrad& p, int ks, void* ws, size_t ws_bytes
   const double flops = 2.0 * 128 * (double)p.B * p.L * (p.Cin * ks + (p.dbias ? 1 : 0));
   M2dProfScope prof(M2D_FAM_GEMM, stream, flops, 0.0, what, 128, p.Cin * ks + (p.dbias ? 1 : 0), p.B * p.L);
   const size_t lds = Cfg::lds_bytes();
+  m2d_route_hit(M2D_RT_tcn_wgrad);
   auto go = [&](auto kern) -> int {
     static bool attr_set = false;
     if (!attr_set) {

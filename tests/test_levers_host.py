@@ -4,7 +4,8 @@ environment-variable names and nothing else, loads no library and needs no GPU.
 (a) the names the package reads through its helpers (m2d_env_* of csrc/m2d_common.h, levers.* of levers.py) are the first
     column of the Levers table plus the configuration rows the package reads;
 (b) no read of an M2D_* variable remains in the package outside those helpers;
-(c) every M2D_* variable bench.py, tools/ or tests/ sets or reads has a row in one of the two tables."""
+(c) every M2D_* variable bench.py, tools/ or tests/ sets or reads has a row in one of the two tables;
+(d) every lever of the table has an arm of tests/lever_cases.py that runs its other position, or a stated exemption."""
 import glob
 import os
 import re
@@ -102,3 +103,14 @@ def test_names_used_by_bench_tools_and_tests_are_listed():
     assert "M2D_LIB" in used and "M2D_MANUAL_CRITIC" in used, "the scan lost the names it is known to meet"
     missing = {n: sorted(f) for n, f in used.items() if n not in listed}
     assert not missing, "not in DESIGN.md's Levers tables: %s" % missing
+
+
+def test_every_lever_has_an_arm_or_an_exemption():
+    from tests import lever_cases
+    levers, _ = _tables()
+    in_arms = {n for a in lever_cases.ARMS.values() for n in a.env}
+    exempt = set(lever_cases.EXEMPT)
+    assert not (in_arms & exempt), "both an arm and an exemption: %s" % sorted(in_arms & exempt)
+    assert in_arms | exempt == set(levers), ("no arm and no exemption: %s; not a lever of the table: %s"
+                                            % (sorted(set(levers) - in_arms - exempt), sorted((in_arms | exempt) - set(levers))))
+    assert all(isinstance(r, str) and len(r) > 10 for r in lever_cases.EXEMPT.values())
