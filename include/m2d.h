@@ -402,6 +402,17 @@ typedef struct M2dAdamItem {
 } M2dAdamItem;
 int m2d_adam_multi(const M2dAdamItem* items, int n, float lr, float beta1, float beta2, float eps, float bias_corr1,
                    float bias_corr2_sqrt, const float* skip, void* stream);
+/* The same step with an exponential moving average of the parameters kept in the same launch (40 tensors per launch):
+ * `ema` is a HOST array of n device pointers, ema[i] the shadow of items[i].param (same element count) or NULL for a
+ * tensor stepped without one; a NULL `ema` with n > 0 is M2D_ERR_ARG. After p has been updated exactly as above
+ * (p, exp_avg, exp_avg_sq and both packed images are bit-identical to m2d_adam_multi's), per element and in fp32, from
+ * the register copy of the fresh p:
+ *   e = e + ema_one_minus_decay * (p - e)
+ * The shadow's alignment counts with the other pointers' (a shadow off 16 bytes is never read as a vector). `skip`
+ * voids the shadows' update with the step. */
+int m2d_adam_multi_ema(const M2dAdamItem* items, float* const* ema, int n, float lr, float beta1, float beta2,
+                       float eps, float bias_corr1, float bias_corr2_sqrt, float ema_one_minus_decay,
+                       const float* skip, void* stream);
 
 /* ---- U-Net encoder resampling (phase3/archis/default.py:235-245) --------------------------- */
 int m2d_maxpool2_fwd(const float* x, float* y, size_t rows, int L, void* stream);

@@ -287,11 +287,36 @@ __global__ void __launch_bounds__(256) m2d_affine_cols_kernel(const float* x, co
 #define M2D_ADAM_TJ 256
 #define M2D_ADAM_VEC 1   // reserved bit 0: every pointer 16-byte aligned
 #define M2D_ADAM_TILE 2  // reserved bit 1: tile mode (packed images, cin * ks a multiple of 4, aligned)
-struct M2dAdamBatch {
-  M2dAdamItem it[M2D_ADAM_BATCH];
-  int first_block[M2D_ADAM_BATCH + 1];
+// EMA form (m2d_adam_multi_ema): every tensor may carry a shadow e (an exponential moving average of p), updated from
+// the register copy of the fresh p in the same pass: e = e + omd * (p - e), + 8 bytes per element. The shadow pointers
+// travel behind the records; 48 of them would bring the argument block to ~4 080 of the 4 096 bytes a launch may carry,
+// so the EMA form steps 40 tensors per launch (static_asserts below).
+#define M2D_ADAM_EMA_BATCH 40
+template <int NB, bool EMA>
+struct M2dAdamBatchT {
+  M2dAdamItem it[NB];
+  int first_block[NB + 1];
   int n;
 };
+template <int NB>
+struct M2dAdamBatchT<NB, true> {
+  M2dAdamItem it[NB];
+  int first_block[NB + 1];
+  int n;
+  float* ema[NB];   // shadow of it[i].param or NULL
+};
+typedef M2dAdamBatchT<M2D_ADAM_BATCH, false> M2dAdamBatch;
+typedef M2dAdamBatchT<M2D_ADAM_EMA_BATCH, true> M2dAdamEmaBatch;
+// the whole argument block of a launch as the kernel declares it (batch, six floats, the skip pointer)
+template <class B>
+struct M2dAdamArgs {
+  B b;
+  float lr_over_bc1, beta1, beta2, eps, bc2_sqrt, omd;
+  const float* skip;
+};
+static_assert(sizeof(M2dAdamBatch) == 48 * 72 + 49 * 4 + 4, "m2d_adam_multi: batch record layout");
+static_assert(sizeof(M2dAdamArgs<M2dAdamBatch>) <= 4096, "m2d_adam_multi: kernel arguments exceed 4 096 bytes");
+static_assert(sizeof(M2dAdamArgs<M2dAdamEmaBatch>) <= 4096, "m2d_adam_multi_ema: kernel arguments exceed 4 096 bytes");
 
 __device__ __forceinline__ void m2d_adam_one(float g, float& m, float& v, float& p, float omb1, float beta2, float omb2,
                                              float bc2_sqrt, float eps, float lr_over_bc1) {
@@ -301,8 +326,13 @@ __device__ __forceinline__ void m2d_adam_one(float g, float& m, float& v, float&
   p = p - lr_over_bc1 * (m / denom);
 }
 
-__global__ void __launch_bounds__(256) m2d_adam_multi_kernel(const M2dAdamBatch b, float lr_over_bc1, float beta1, float beta2,
-                                                             float eps, float bc2_sqrt, const float* skip) {
+// the shadow's update from the register copy of the fresh parameter
+__device__ __forceinline__ float m2d_ema_one(float e, float p, float omd) { return e + omd * (p - e); }
+
+template <bool EMA>
+__global__ void __launch_bounds__(256) m2d_adam_multi_kernel(const M2dAdamBatchT<EMA ? M2D_ADAM_EMA_BATCH : M2D_ADAM_BATCH, EMA> b,
+                                                             float lr_over_bc1, float beta1, float beta2, float eps,
+                                                             float bc2_sqrt, float omd, const float* skip) {
   // (any non-zero BIT pattern counts: the word may be an unsigned flag, e.g. m2d_async_fault_word(); read past the
   // caches - it can be raised by a kernel that ran just before)
   if (skip && __hip_atomic_load((const unsigned*)skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
@@ -310,6 +340,8 @@ __global__ void __launch_bounds__(256) m2d_adam_multi_kernel(const M2dAdamBatch 
   int k = 0;
   while (k + 1 < b.n && (int)blockIdx.x >= b.first_block[k + 1]) ++k;   // wave-uniform
   const M2dAdamItem& t = b.it[k];
+  float* sh = nullptr;   // this tensor's shadow (wave-uniform; NULL: stepped without one)
+  if constexpr (EMA) sh = b.ema[k];
   const int lb = (int)blockIdx.x - b.first_block[k];
   const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
   const int tid = threadIdx.x;
@@ -334,6 +366,13 @@ __global__ void __launch_bounds__(256) m2d_adam_multi_kernel(const M2dAdamBatch 
         *reinterpret_cast<float4*>(t.exp_avg + i) = m;
         *reinterpret_cast<float4*>(t.exp_avg_sq + i) = v;
         *reinterpret_cast<float4*>(t.param + i) = p;
+        if constexpr (EMA)
+          if (sh) {
+            float4 s = *reinterpret_cast<const float4*>(sh + i);
+            s.x = m2d_ema_one(s.x, p.x, omd); s.y = m2d_ema_one(s.y, p.y, omd);
+            s.z = m2d_ema_one(s.z, p.z, omd); s.w = m2d_ema_one(s.w, p.w, omd);
+            *reinterpret_cast<float4*>(sh + i) = s;
+          }
         P[r][4 * c4] = p.x; P[r][4 * c4 + 1] = p.y; P[r][4 * c4 + 2] = p.z; P[r][4 * c4 + 3] = p.w;
       }
     }
@@ -376,11 +415,20 @@ __global__ void __launch_bounds__(256) m2d_adam_multi_kernel(const M2dAdamBatch 
         *reinterpret_cast<float4*>(t.exp_avg + i) = m;
         *reinterpret_cast<float4*>(t.exp_avg_sq + i) = v;
         *reinterpret_cast<float4*>(t.param + i) = p;
+        if constexpr (EMA)
+          if (sh) {
+            float4 s = *reinterpret_cast<const float4*>(sh + i);
+            s.x = m2d_ema_one(s.x, p.x, omd); s.y = m2d_ema_one(s.y, p.y, omd);
+            s.z = m2d_ema_one(s.z, p.z, omd); s.w = m2d_ema_one(s.w, p.w, omd);
+            *reinterpret_cast<float4*>(sh + i) = s;
+          }
       } else {
         for (long long q = i; q < t.numel && q < i + 4; ++q) {
           float m = t.exp_avg[q], v = t.exp_avg_sq[q], p = t.param[q];
           m2d_adam_one(t.grad[q], m, v, p, omb1, beta2, omb2, bc2_sqrt, eps, lr_over_bc1);
           t.exp_avg[q] = m; t.exp_avg_sq[q] = v; t.param[q] = p;
+          if constexpr (EMA)
+            if (sh) sh[q] = m2d_ema_one(sh[q], p, omd);
         }
       }
     }
@@ -397,6 +445,8 @@ __global__ void __launch_bounds__(256) m2d_adam_multi_kernel(const M2dAdamBatch 
     t.exp_avg[i] = m;
     t.exp_avg_sq[i] = v;
     t.param[i] = p;
+    if constexpr (EMA)
+      if (sh) sh[i] = m2d_ema_one(sh[i], p, omd);
     if (t.pack_fwd || t.pack_bwd) {  // (co, ci, kk) -> (ci, kk, co) and (co, kk, ci)
       const int kk = (int)(i % t.ks);
       const long long r = i / t.ks;
@@ -747,6 +797,60 @@ static unsigned grid_for(size_t n, unsigned cap = 2048) {
   return (unsigned)b;
 }
 
+// torch.optim.Adam's step over many tensors (see include/m2d.h); `items` (and `ema`) are HOST arrays. One body for
+// both entry points: EMA = false is m2d_adam_multi as it always was (same records, same arm per tensor, same grid).
+template <bool EMA>
+static int adam_multi_launch(const char* name, const M2dAdamItem* items, float* const* ema, int n, float lr, float beta1,
+                             float beta2, float eps, float bias_corr1, float bias_corr2_sqrt, float omd, const float* skip,
+                             hipStream_t stream) {
+  constexpr int NB = EMA ? M2D_ADAM_EMA_BATCH : M2D_ADAM_BATCH;
+  if (n < 0 || (n > 0 && !items) || (EMA && n > 0 && !ema) || !(bias_corr1 > 0.f) || !(bias_corr2_sqrt > 0.f))
+    M2D_FAIL(M2D_ERR_ARG, "%s: bad arguments", name);
+  double bytes = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const M2dAdamItem& t = items[i];
+    if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel < 0)
+      M2D_FAIL(M2D_ERR_ARG, "%s: item %d has a NULL tensor", name, i);
+    if ((t.pack_fwd || t.pack_bwd) && (t.cout <= 0 || t.cin <= 0 || t.ks <= 0 || (long long)t.cout * t.cin * t.ks != t.numel))
+      M2D_FAIL(M2D_ERR_ARG, "%s: item %d: packed images need the (cout, cin, ks) of the weight", name, i);
+    bytes += ((EMA && ema[i]) ? 36.0 : 28.0) * (double)t.numel +
+             4.0 * (double)t.numel * ((t.pack_fwd ? 1 : 0) + (t.pack_bwd ? 1 : 0));
+  }
+  M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, bytes, EMA ? "adam_multi_ema" : "adam_multi");
+  for (int i0 = 0; i0 < n;) {
+    M2dAdamBatchT<NB, EMA> b;
+    b.n = 0;
+    int blocks = 0;
+    for (; i0 < n && b.n < NB; ++i0) {
+      if (items[i0].numel == 0) continue;
+      M2dAdamItem& t = b.it[b.n];
+      t = items[i0];
+      uintptr_t bits = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
+      if constexpr (EMA) {
+        // the shadow is read and written with the parameter's accesses: its alignment decides the arm with theirs
+        b.ema[b.n] = ema[i0];
+        bits |= (uintptr_t)ema[i0];
+      }
+      const bool al = (bits & 15u) == 0;
+      const bool packed = t.pack_fwd || t.pack_bwd;
+      const bool tile = packed && al && ((t.cin * t.ks) % 4) == 0;
+      t.reserved = tile ? M2D_ADAM_TILE : ((al && !packed) ? M2D_ADAM_VEC : 0);
+      b.first_block[b.n] = blocks;
+      if (tile)
+        blocks += ((t.cout + M2D_ADAM_TCO - 1) / M2D_ADAM_TCO) * ((t.cin * t.ks + M2D_ADAM_TJ - 1) / M2D_ADAM_TJ);
+      else
+        blocks += (int)((t.numel + M2D_ADAM_CHUNK - 1) / M2D_ADAM_CHUNK);
+      ++b.n;
+    }
+    b.first_block[b.n] = blocks;
+    if (blocks == 0) continue;
+    hipLaunchKernelGGL(m2d_adam_multi_kernel<EMA>, dim3((unsigned)blocks), dim3(256), 0, stream, b, lr / bias_corr1, beta1,
+                       beta2, eps, bias_corr2_sqrt, omd, skip);
+    M2D_CHECK_LAUNCH(name);
+  }
+  return M2D_OK;
+}
+
 extern "C" {
 
 // losses.py:13-20 — interpolation between real and fake with one alpha per sample.
@@ -872,48 +976,18 @@ int m2d_affine_cols(const float* x, const float* scale, const float* shift, floa
   return M2D_OK;
 }
 
-// torch.optim.Adam's step over many tensors (see include/m2d.h); `items` is a HOST array
+// torch.optim.Adam's step over many tensors, without and with shadows (adam_multi_launch above)
 int m2d_adam_multi(const M2dAdamItem* items, int n, float lr, float beta1, float beta2, float eps, float bias_corr1,
                    float bias_corr2_sqrt, const float* skip, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n < 0 || (n > 0 && !items) || !(bias_corr1 > 0.f) || !(bias_corr2_sqrt > 0.f))
-    M2D_FAIL(M2D_ERR_ARG, "m2d_adam_multi: bad arguments");
-  double bytes = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const M2dAdamItem& t = items[i];
-    if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel < 0)
-      M2D_FAIL(M2D_ERR_ARG, "m2d_adam_multi: item %d has a NULL tensor", i);
-    if ((t.pack_fwd || t.pack_bwd) && (t.cout <= 0 || t.cin <= 0 || t.ks <= 0 || (long long)t.cout * t.cin * t.ks != t.numel))
-      M2D_FAIL(M2D_ERR_ARG, "m2d_adam_multi: item %d: packed images need the (cout, cin, ks) of the weight", i);
-    bytes += 28.0 * (double)t.numel + 4.0 * (double)t.numel * ((t.pack_fwd ? 1 : 0) + (t.pack_bwd ? 1 : 0));
-  }
-  M2dProfScope prof(M2D_FAM_POINTWISE, stream, 0.0, bytes, "adam_multi");
-  for (int i0 = 0; i0 < n;) {
-    M2dAdamBatch b;
-    b.n = 0;
-    int blocks = 0;
-    for (; i0 < n && b.n < M2D_ADAM_BATCH; ++i0) {
-      if (items[i0].numel == 0) continue;
-      M2dAdamItem& t = b.it[b.n];
-      t = items[i0];
-      const bool al = ((((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq) & 15u) == 0);
-      const bool packed = t.pack_fwd || t.pack_bwd;
-      const bool tile = packed && al && ((t.cin * t.ks) % 4) == 0;
-      t.reserved = tile ? M2D_ADAM_TILE : ((al && !packed) ? M2D_ADAM_VEC : 0);
-      b.first_block[b.n] = blocks;
-      if (tile)
-        blocks += ((t.cout + M2D_ADAM_TCO - 1) / M2D_ADAM_TCO) * ((t.cin * t.ks + M2D_ADAM_TJ - 1) / M2D_ADAM_TJ);
-      else
-        blocks += (int)((t.numel + M2D_ADAM_CHUNK - 1) / M2D_ADAM_CHUNK);
-      ++b.n;
-    }
-    b.first_block[b.n] = blocks;
-    if (blocks == 0) continue;
-    hipLaunchKernelGGL(m2d_adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, b, lr / bias_corr1, beta1, beta2,
-                       eps, bias_corr2_sqrt, skip);
-    M2D_CHECK_LAUNCH("m2d_adam_multi");
-  }
-  return M2D_OK;
+  return adam_multi_launch<false>("m2d_adam_multi", items, nullptr, n, lr, beta1, beta2, eps, bias_corr1, bias_corr2_sqrt,
+                                  0.f, skip, (hipStream_t)stream_);
+}
+
+int m2d_adam_multi_ema(const M2dAdamItem* items, float* const* ema, int n, float lr, float beta1, float beta2, float eps,
+                       float bias_corr1, float bias_corr2_sqrt, float ema_one_minus_decay, const float* skip,
+                       void* stream_) {
+  return adam_multi_launch<true>("m2d_adam_multi_ema", items, ema, n, lr, beta1, beta2, eps, bias_corr1, bias_corr2_sqrt,
+                                 ema_one_minus_decay, skip, (hipStream_t)stream_);
 }
 
 // nn.Tanh of the 'tanh' heads and its derivatives (see the kernels): closed under differentiation like the conv ops

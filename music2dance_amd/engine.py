@@ -108,6 +108,7 @@ class WganGpEngine:
         # pass (one autograd backward per generator iteration): only the last bucket's ring is exposed
         self.x_gen = GradExchange(gen.parameters(), bucket_mb=4.0).overlap_backward() if data_parallel else None
         self._critic_step_pending = False
+        self._ema = None   # GeneratorEMA once enable_ema() has been called with a decay
         # a persistent recurrent launch that times out must not take the run with it (_check_async): both optimizers
         # read the fault word - directly, or (data parallel) as reduced over the ranks by their gradient exchange
         k = kernels.impl()
@@ -175,12 +176,44 @@ class WganGpEngine:
             return None
         return x.poll
 
+    # -- averaged generator (ema.py): shadows of the generator's parameters, moved inside its fused Adam launch
+    def enable_ema(self, decay, warmup=True):
+        """Keep an exponential moving average of the generator's weights from here on: `gen_ema` is a twin generator
+        whose parameters the generator's optimizer step updates in its own launch. decay 0 / None: off (the default -
+        nothing changes). Idempotent; the critic is never averaged."""
+        if not decay:
+            self._ema = None
+            return self
+        if self._ema is not None and self._ema.decay == float(decay) and self._ema.warmup == bool(warmup):
+            return self
+        if not hasattr(self.optim_gen, "track_ema"):
+            raise RuntimeError("ema_decay needs the fused optimizer step (optim.Adam); with M2D_ADAM=torch there is "
+                               "none to keep the average in")
+        from .ema import GeneratorEMA
+        self._ema = GeneratorEMA(self.gen, self.optim_gen, decay, warmup=warmup)
+        return self
+
+    @property
+    def gen_ema(self):
+        """The averaged generator (eval mode, BatchNorm buffers as the live generator's now), or None when EMA is off"""
+        if self._ema is None:
+            return None
+        if self._gen_stream is not None:
+            # the live BatchNorm buffers are written by generator forwards on the generator stream
+            torch.cuda.current_stream().wait_stream(self._gen_stream)
+        return self._ema.module()
+
     def _gen_step(self):
         if self.x_gen is not None:
             self.x_gen.exchange()
+        ema = self._ema
+        if ema is not None:
+            self.optim_gen.ema_decay = ema.next_decay()
         self.optim_gen.step()
         self._gen_epoch += 1
         kernels.impl().invalidate_packed(self._gen_params)
+        if ema is not None:
+            ema.stepped()   # counts the update, drops the twin's cached weight images
         if self._gen_stream is not None:
             self._gen_params_ready = torch.cuda.current_stream().record_event()
 
@@ -629,18 +662,20 @@ class Phase3Engine(WganGpEngine):
         g["noise_g"].copy_(to_device_async(torch.randn(B, T, self.gen.noise_size), real.device))
 
     @torch.no_grad()
-    def validation_l1(self, batches):
+    def validation_l1(self, batches, gen=None):
         """Eval-mode L1 validation loss (phase3/train.py:245-261): mean over batches of
-        L1(real, gen(audio_slices)) with the generator's running BatchNorm statistics."""
-        was_training = self.gen.training
-        self.gen.eval()
+        L1(real, gen(audio_slices)) with the generator's running BatchNorm statistics.
+        gen: another generator to score on the same batches (the averaged one, engine.gen_ema)."""
+        gen = self.gen if gen is None else gen
+        was_training = gen.training
+        gen.eval()
         vals = []
         for real, audio_slices in batches:
             B = real.size(0)
             T = real.numel() // (B * self.output_size)
-            fake_rows = self.gen(audio_slices, [T] * B)
+            fake_rows = gen(audio_slices, [T] * B)
             vals.append(ops.l1_mean(real.reshape(B * T, self.output_size).contiguous(), fake_rows))
-        self.gen.train(was_training)
+        gen.train(was_training)
         return torch.stack(vals).mean()
 
 

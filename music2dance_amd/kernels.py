@@ -598,14 +598,19 @@ class HipKernels:
         _launch("m2d_tanh_bwd_bwd", dev, _ptr(g), _ptr(gy), _ptr(y), _ptr(out), y.numel())
         return out
 
-    def adam_multi(self, params, grads, exp_avgs, exp_avg_sqs, lr, beta1, beta2, eps, step, skip=None, repack=True):
+    def adam_multi(self, params, grads, exp_avgs, exp_avg_sqs, lr, beta1, beta2, eps, step, skip=None, repack=True,
+                   ema=None, ema_decay=None):
         """One torch.optim.Adam step (defaults: no weight decay, no amsgrad) over the listed tensors in one launch per 48
         (include/m2d.h: m2d_adam_multi). repack: conv weights (3-D, >= 16 input channels) that have live packed images in
         the weight cache get those images rewritten in the same pass - the cache entries stay valid across the step
-        (the engines call invalidate_packed() for everything else). skip: optional device float (non-zero = no-op)."""
+        (the engines call invalidate_packed() for everything else). skip: optional device float (non-zero = no-op).
+        ema: a list parallel to `params` of shadow tensors (or None per tensor) that the same launch moves towards the
+        fresh parameters, e += (1 - ema_decay) * (p - e) (m2d_adam_multi_ema, one launch per 40); their cached images
+        are NOT rewritten - the caller drops them with invalidate_packed(). ema=None: m2d_adam_multi."""
         if not params:
             return
-        dev = _chk(*params, *grads, *exp_avgs, *exp_avg_sqs, skip if torch.is_tensor(skip) else None)
+        shadows = () if ema is None else [e for e in ema if e is not None]
+        dev = _chk(*params, *grads, *exp_avgs, *exp_avg_sqs, *shadows, skip if torch.is_tensor(skip) else None)
         items = (_lib.AdamItem * len(params))()
         keep = []
         for it, p, g, m, v in zip(items, params, grads, exp_avgs, exp_avg_sqs):
@@ -622,8 +627,20 @@ class HipKernels:
                 keep.append((key, (ent[0], p._version, None, ent[3])))
         bc1 = 1.0 - beta1 ** step
         bc2s = (1.0 - beta2 ** step) ** 0.5
-        _launch("m2d_adam_multi", dev, ctypes.addressof(items), len(params), lr, beta1, beta2, eps, bc1, bc2s,
-                (skip if isinstance(skip, int) else _ptr(skip)) or 0)
+        skip_word = (skip if isinstance(skip, int) else _ptr(skip)) or 0
+        if ema is None:
+            _launch("m2d_adam_multi", dev, ctypes.addressof(items), len(params), lr, beta1, beta2, eps, bc1, bc2s,
+                    skip_word)
+        else:
+            if ema_decay is None or len(ema) != len(params):
+                raise _lib.M2dError("adam_multi: ema needs ema_decay and one entry (tensor or None) per parameter")
+            for p, e in zip(params, ema):
+                if e is not None and (e.numel() != p.numel() or e.data_ptr() == p.data_ptr()):
+                    raise _lib.M2dError("adam_multi: a shadow has its parameter's element count and storage of its own")
+            shadow_ptrs = (ctypes.c_void_p * len(params))(*[None if e is None else e.data_ptr() for e in ema])
+            omd = 1.0 - float(ema_decay)   # (rounded to fp32 once, by the call)
+            _launch("m2d_adam_multi_ema", dev, ctypes.addressof(items), ctypes.addressof(shadow_ptrs), len(params), lr,
+                    beta1, beta2, eps, bc1, bc2s, omd, skip_word)
         for key, ent in keep:
             self._packed[key] = ent
         # (accumulated over the launches of one optimizer step - several step groups / 48-tensor batches - and consumed

@@ -7,7 +7,12 @@ arithmetic: every parameter of a group that has a gradient is stepped by the sam
 skipped and get no state, SURVEY.md A.5: the dead `fc1` / `bn1` affine of every LinearBlock), and conv weights whose
 K-major packed images are live in the kernel layer's weight cache have those images rewritten in the same pass (the
 critic's weights change every loop body: one launch instead of Adam's three plus a pack launch per conv).
-`skip_flag`: optional device float; non-zero at execution time = the step is a no-op on the device."""
+`skip_flag`: optional device float; non-zero at execution time = the step is a no-op on the device.
+
+`track_ema(pairs)` + `ema_decay`: the same launch keeps an exponential moving average of the parameters it steps in
+shadow tensors of the caller's (m2d_adam_multi_ema: e += (1 - ema_decay) * (p - e) from the register copy of the fresh
+p). A parameter that is not stepped (no gradient) leaves its shadow alone. The shadows are not optimizer state:
+`state_dict()` is what it is without them."""
 import torch
 
 from . import kernels
@@ -17,6 +22,21 @@ class Adam(torch.optim.Adam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False, foreach=False, fused=False)
         self.skip_flag = None
+        self.ema_decay = None   # set by the caller before each step; None = this step leaves the shadows alone
+        self._ema = {}          # parameter -> its shadow (track_ema)
+
+    def track_ema(self, pairs):
+        """pairs: iterable of (parameter of this optimizer, shadow tensor): same shape, dtype and device, storage of
+        its own. From now on every step with `ema_decay` set moves the shadow of each parameter it steps."""
+        own = {id(p) for g in self.param_groups for p in g["params"]}
+        for p, e in pairs:
+            if id(p) not in own:
+                raise ValueError("track_ema: not a parameter of this optimizer")
+            if e.shape != p.shape or e.dtype != p.dtype or e.device != p.device or not e.is_contiguous():
+                raise ValueError("track_ema: a shadow has its parameter's shape, dtype and device and is contiguous")
+            if e.data_ptr() == p.data_ptr() or e.requires_grad:
+                raise ValueError("track_ema: a shadow has storage of its own and takes no gradient")
+            self._ema[p] = e
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -26,6 +46,9 @@ class Adam(torch.optim.Adam):
                 loss = closure()
         k = kernels.impl()
         skip = self.skip_flag
+        decay = self.ema_decay if self._ema else None
+        if decay is not None and not 0.0 <= float(decay) <= 1.0:
+            raise ValueError("ema_decay must lie in [0, 1], got %r" % (decay,))
         if isinstance(skip, int) and skip:
             # the LIVE fault word: a recurrent launch on another stream (the generator forward runs one iteration ahead)
             # may raise it while this step's launches execute, and workgroups that read it before / after would apply /
@@ -59,6 +82,10 @@ class Adam(torch.optim.Adam):
             # (parameters that got their first gradient later than the others carry their own step count)
             for step, rows in by_step.items():
                 ps, gs, ms, vs = zip(*rows)
-                k.adam_multi(list(ps), list(gs), list(ms), list(vs), lr, beta1, beta2, group["eps"], step,
-                             skip=skip)
+                if decay is None:
+                    k.adam_multi(list(ps), list(gs), list(ms), list(vs), lr, beta1, beta2, group["eps"], step,
+                                 skip=skip)
+                else:
+                    k.adam_multi(list(ps), list(gs), list(ms), list(vs), lr, beta1, beta2, group["eps"], step,
+                                 skip=skip, ema=[self._ema.get(p) for p in ps], ema_decay=float(decay))
         return loss

@@ -7,6 +7,8 @@ reference reads an undefined `file` variable, phase1/train_wgan-gp.py:31). The h
 script name of the reference is not importable as a module; `train_wgan-gp.py` next to this
 file forwards to it.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -21,9 +23,10 @@ def parser():
         "per body at batch 64); results equal the eager path's. Default on one GPU"))
 
 
-def checkpoints(epoch):
+def checkpoints(epoch, ema=False):
+    """ema: the run keeps an averaged generator (YAML `ema_decay`), saved as gen_ema_<n>.pt beside gen_<n>.pt"""
     n = epoch + 1
-    return [("gen", "gen_%d.pt" % n), ("critic", "critic_%d.pt" % n)] if n % 5 == 0 else []
+    return runner.with_ema([("gen", "gen_%d.pt" % n), ("critic", "critic_%d.pt" % n)] if n % 5 == 0 else [], ema)
 
 
 def scalars(out):
@@ -54,6 +57,7 @@ def main(argv=None):
                 torch.distributed.broadcast(t.data, 0)
         torch.manual_seed(torch.initial_seed() + run.rank)
     engine.host_noise = False  # phase1/train_wgan-gp.py:83 draws the noise on the device
+    ema = runner.enable_ema(engine, cfg)   # (after the broadcast: the twin copies the common weights)
     if runner.graphs_on(run):
         engine.enable_graphs()
 
@@ -68,7 +72,7 @@ def main(argv=None):
         return (((b,), None) for b, _ in runner.resident_batches(loader, device))
 
     # (the reference's phase 1 writes no model_*.txt)
-    runner.train(run, logdir, engine, batches, scalars, checkpoints, architectures=False)
+    runner.train(run, logdir, engine, batches, scalars, functools.partial(checkpoints, ema=ema), architectures=False)
     return engine
 
 

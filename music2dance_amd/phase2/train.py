@@ -9,6 +9,8 @@ Flags -c/-d/-n/-f and YAML keys as in the reference's phase2/train.py. `wgangp` 
 torch), a generator step and both scheduler steps on every iteration, scalars logged as loss_D / loss_G. Both keep this
 port's checkpoint schedule (gpgen_ / gpcritic_ every 5000 epochs). Any other value raises the reference's error.
 """
+import functools
+
 import torch
 
 from .. import runner
@@ -23,9 +25,10 @@ def parser():
         "sequences / s at batch 32)"))
 
 
-def checkpoints(epoch):
+def checkpoints(epoch, ema=False):
+    """ema: the run keeps an averaged generator (YAML `ema_decay`), saved as gpgen_ema_<n>.pt beside gpgen_<n>.pt"""
     n = epoch + 1
-    return [("gen", "gpgen_%d.pt" % n), ("critic", "gpcritic_%d.pt" % n)] if n % 5000 == 0 else []
+    return runner.with_ema([("gen", "gpgen_%d.pt" % n), ("critic", "gpcritic_%d.pt" % n)] if n % 5000 == 0 else [], ema)
 
 
 def wgangp_scalars(out):
@@ -61,6 +64,7 @@ def main(argv=None):
     engine = (Phase2GanEngine if gan else Phase2Engine)(gen, critic, cfg, sync_bn=opts.sync_bn)
     torch.manual_seed(run.rank)  # identical weights (seed 0 above), rank-distinct noise / alpha draws
     engine.host_noise = False  # phase2/train.py:139-140 draws the noise on the device
+    ema = runner.enable_ema(engine, cfg)
     if runner.graphs_on(run):
         engine.enable_graphs()
 
@@ -77,7 +81,8 @@ def main(argv=None):
         return (((b[0].reshape(b[0].size(0), stick_length, -1),), None)
                 for b, _ in runner.resident_batches(loader, device))
 
-    runner.train(run, logdir, engine, batches, gan_scalars if gan else wgangp_scalars, checkpoints)
+    runner.train(run, logdir, engine, batches, gan_scalars if gan else wgangp_scalars,
+                 functools.partial(checkpoints, ema=ema))
     return engine
 
 

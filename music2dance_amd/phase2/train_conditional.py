@@ -11,6 +11,8 @@ Logs loss_critic / loss_gen / gp / w_dist with the reference's signs and saves g
 Only `wgangp` runs: the reference's conditional `gan` branch needs the auxiliary head the archis do not have (and
 maximises its real-row BCE); any other value raises the reference's error.
 """
+import functools
+
 import torch
 
 from .. import runner
@@ -46,6 +48,7 @@ def main(argv=None):
     engine = Phase2CondEngine(gen, critic, cfg, sync_bn=opts.sync_bn)
     torch.manual_seed(run.rank)  # identical weights (seed 0 above), rank-distinct draws
     engine.host_noise = False  # labels, noise, alpha and dropout masks on the device
+    ema = runner.enable_ema(engine, cfg)
 
     def synthetic(seed):  # random poses and random styles
         g = torch.Generator().manual_seed(seed)
@@ -62,7 +65,8 @@ def main(argv=None):
         return (((b[0].reshape(b[0].size(0), stick_length, -1), b[2]), None)
                 for b, _ in runner.resident_batches(loader, device))
 
-    runner.train(run, logdir, engine, batches, scalars, checkpoints, train_mode=("gen", "critic"))
+    runner.train(run, logdir, engine, batches, scalars, functools.partial(checkpoints, ema=ema),
+                 train_mode=("gen", "critic"))
     return engine
 
 

@@ -5,6 +5,8 @@
 Same flags (-c/-d/-n), YAML keys, seeds, scalar tags and checkpoint names as the
 reference's phase3/train.py; the loop body is engine.Phase3Engine.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -34,11 +36,12 @@ def parser():
     return ap
 
 
-def checkpoints(epoch):
+def checkpoints(epoch, ema=False):
+    """ema: the run keeps an averaged generator (YAML `ema_decay`), saved as gpgen_ema_<n>.pt beside gpgen_<n>.pt"""
     n = epoch + 1
     if n % 5000 == 0:
-        return [("gen", "gpgen_%d.pt" % n), ("critic", "gpcritic_%d.pt" % n)]
-    return [("gen", "gpgen_%d.pt" % n)] if n <= 1000 and n % 100 == 0 else []
+        return runner.with_ema([("gen", "gpgen_%d.pt" % n), ("critic", "gpcritic_%d.pt" % n)], ema)
+    return runner.with_ema([("gen", "gpgen_%d.pt" % n)] if n <= 1000 and n % 100 == 0 else [], ema)
 
 
 def scalars(out):
@@ -67,6 +70,7 @@ def main(argv=None):
         window, hop = int(cfg["window_size"] * dataset.aud_rate), dataset.ratio
     gen, critic = build(cfg, device, stick_length)
     engine = Phase3Engine(gen, critic, cfg, ablated=cfg["ablated"], sync_bn=opts.sync_bn)
+    ema = runner.enable_ema(engine, cfg)
     # seed 0 built identical weights on every rank; the in-loop host draws (generator noise,
     # penalty alpha) must differ between ranks, as they do between samples of one global batch
     torch.manual_seed(run.rank)
@@ -112,13 +116,17 @@ def main(argv=None):
         # validation_l1 restores train mode
         e_val = engine.validation_l1(val_batches())
         log.scalars({"l1_loss_val": e_val}, engine.total_iterations, force=True)
+        if ema:   # the averaged generator on the same held-out batches (a tag of this port's; the reference's stay)
+            log.scalars({"l1_loss_val_ema": engine.validation_l1(val_batches(), gen=engine.gen_ema)},
+                        engine.total_iterations, force=True)
         if (epoch + 1) % 500 == 0 and run.rank == 0 and not done:
             o = engine.last_full
             print("Iteration: {} LossG : {} LossD : {} L1 train : {} L1 val : {}".format(
                 engine.total_iterations, float(o.get("loss_gen", float("nan"))), float(o["loss_critic"]),
                 float(o.get("l1_loss_train", float("nan"))), float(e_val)))
 
-    runner.train(run, logdir, engine, batches, scalars, checkpoints, started=started, epoch_end=validate)
+    runner.train(run, logdir, engine, batches, scalars, functools.partial(checkpoints, ema=ema), started=started,
+                 epoch_end=validate)
     return engine
 
 

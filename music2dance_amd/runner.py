@@ -274,6 +274,27 @@ def graphs_on(run):
     return run.device.type == "cuda" and (run.opts.graphs or (run.world == 1 and not run.opts.no_graphs))
 
 
+def enable_ema(engine, cfg):
+    """The YAML keys `ema_decay` (a float; absent, null or 0: off) and `ema_warmup` (default true) -> engine.enable_ema;
+    -> whether the engine now keeps an averaged generator (engine.gen_ema)."""
+    engine.enable_ema(cfg.get("ema_decay"), warmup=bool(cfg.get("ema_warmup", True)))
+    return engine.gen_ema is not None
+
+
+def with_ema(due, ema):
+    """A script's due checkpoints [(module name, file name)]; with `ema`, ("gen", "<stem>_<n>.pt") is followed by
+    ("gen_ema", "<stem>_ema_<n>.pt"): the averaged generator as an ordinary generator state_dict."""
+    if not ema:
+        return due
+    out = []
+    for name, file in due:
+        out.append((name, file))
+        if name == "gen":
+            stem, n = file.rsplit("_", 1)
+            out.append(("gen_ema", "%s_ema_%s" % (stem, n)))
+    return out
+
+
 def train(run, logdir, engine, batches, scalars, checkpoints, train_mode=("gen",), architectures=True, started=None,
           epoch_end=None):
     """The loop of a train script, from the built engine to the closing print.

@@ -1,5 +1,5 @@
 """The scoring driver of the scripts that use a trained generator (phase1.evaluate, phase2.evaluate, phase3.evaluate and
-phase3.generate), as runner.py is the training driver: the constants, the six common flags (`add_common_flags`), the
+phase3.generate), as runner.py is the training driver: the constants, the common flags (`add_common_flags`), the
 checkpoint and classifier loaders, the shared `main` (`run`), strict JSON (`json_safe`), the validation-take lookup and
 the scores more than one script computes (`confusion`, `jerk_stats`, `jerk_per_sequence`, `distribution_scores`). A
 script keeps its docstring, its own flags and their checks, its networks, its seeds and the order of its result's keys.
@@ -21,8 +21,9 @@ N_STYLES = 4
 
 # ------------------------------------------------------------------------------------------- the command line
 def add_common_flags(ap, phase, stem, synthetic="random inputs of the dataset's shapes", source=None):
-    """The six flags every scoring script takes: -c, -l, --gen-weights, --synthetic, --folder, -d. `synthetic`: what
-    that flag means to the script; `source`: the (mutually exclusive) group --synthetic joins instead of the parser."""
+    """The flags every scoring script takes: -c, -l, --gen-weights, --synthetic, --folder, -d, and --ema (score the
+    averaged generator a run with `ema_decay` saved). `synthetic`: what that flag means to the script; `source`: the
+    (mutually exclusive) group --synthetic joins instead of the parser."""
     ap.add_argument("-c", "--config", type=str, required=True, help="phase-%d config file of the generator" % phase)
     ap.add_argument("-l", "--logdir", type=str, required=True, help="run directory of the generator")
     ap.add_argument("--gen-weights", type=str, default=None,
@@ -30,6 +31,9 @@ def add_common_flags(ap, phase, stem, synthetic="random inputs of the dataset's 
     (source or ap).add_argument("--synthetic", action="store_true", help=synthetic)
     ap.add_argument("--folder", type=str, default=None, help="dataset folder (overrides the YAML's `folder:`)")
     ap.add_argument("-d", "--device", type=int, default=None, help="choose gpu id")
+    ap.add_argument("--ema", action="store_true",
+                    help="load the averaged generator (latest <logdir>/models/%s_ema_*.pt) instead of the last iterate; "
+                         "--gen-weights still wins" % stem)
 
 
 def json_safe(v):
@@ -72,9 +76,14 @@ def latest_checkpoint(logdir, stem="gpgen"):
 
 
 def load_generator(gen, opts, stem="gpgen"):
-    """--gen-weights, or the latest <logdir>/models/<stem>_*.pt, into `gen`, which is left in eval mode; -> the path,
-    None for the random weights --synthetic allows when there is no checkpoint"""
-    path = opts.gen_weights or latest_checkpoint(opts.logdir, stem)
+    """--gen-weights, or the latest <logdir>/models/<stem>_*.pt (with --ema: <stem>_ema_*.pt, the averaged generator of
+    a run trained with `ema_decay`), into `gen`, which is left in eval mode; -> the path, None for the random weights
+    --synthetic allows when there is no checkpoint"""
+    ema = bool(getattr(opts, "ema", False))
+    path = opts.gen_weights or latest_checkpoint(opts.logdir, stem + "_ema" if ema else stem)
+    if path is None and ema and not opts.synthetic:
+        raise SystemExit("--ema: no averaged-generator checkpoint %s/models/%s_ema_*.pt: train with `ema_decay` set in "
+                         "the YAML, or pass --gen-weights" % (opts.logdir, stem))
     if path is not None:
         if not os.path.exists(path):
             raise SystemExit("generator checkpoint %s not found" % path)
